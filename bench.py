@@ -11,6 +11,11 @@ the device by mmw_synth_cubes before the timed region), a step is one pass of th
 Frames are independent, so there is NO data-path collective (weak scaling): torch.distributed (gloo) is
 used only for the barriers around the timed region and the max-over-ranks of the elapsed time.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the headline.  `--full` adds everything else:
+per-kernel HIP events and rooflines, the in-situ streaming ceiling, the `detect` / `detect_os` sub-records,
+parity of the run against the oracle, and the CPU baselines.  `--dump-outputs DIR` writes what the timed
+path computed in its last step (rank 0's shard) as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -316,6 +321,46 @@ def host_stream_record(ctx, chunk_frames: int = 128, n_chunks: int = 8):
     return out
 
 
+DUMP_SEED = 20240611        # rows sampled from every frame of the chain output (fixed: two builds dump the same cells)
+
+
+def dump_outputs(out_dir, F, d_out=None, work=None):
+    """What the timed path left in its output buffers after its last step, as float32 / float64 .npy files (about 52 MB
+    for the headline's 1250 frames).  Complex arrays are stored as float32 [..., 2] (real, imaginary).
+
+    chain:  ``chain_frames`` [3, A, S, C, 2] = the whole angle-range-Doppler cubes of frames ``chain_frame_index`` (first,
+            middle, last), ``chain_rows`` [F, C, 2] = one seeded (angle bin, range bin) row of every frame, at
+            ``chain_row_index`` [F, 3] = (frame, angle bin, range bin).
+    detect: ``detect_counts`` [F], ``detect_dets`` [n, 3] = (frame, range bin, Doppler bin) of every detection in order,
+            ``detect_az`` / ``detect_el`` [n] = their argmax bins, ``detect_rd_frames`` [3, V, S, C, 2] = the range-Doppler
+            cubes of frames ``detect_frame_index``."""
+    os.makedirs(out_dir, exist_ok=True)
+    picks = sorted({0, F // 2, F - 1})
+    save = lambda name, arr: np.save(os.path.join(out_dir, name + ".npy"), arr)
+    c2f = lambda z: np.ascontiguousarray(z).view(np.float32).reshape(z.shape + (2,))
+    if d_out is not None:
+        save("chain_frame_index", np.array(picks, np.float64))
+        save("chain_frames", np.stack([c2f(d_out.download((A, S, C), np.complex64, f * OUT_BYTES)) for f in picks]))
+        rng = np.random.default_rng(DUMP_SEED)
+        idx = np.stack([np.arange(F), rng.integers(0, A, F), rng.integers(0, S, F)], axis=1)
+        rows = np.stack([d_out.download((C,), np.complex64, f * OUT_BYTES + (a * S + s) * C * 8) for f, a, s in idx.tolist()])
+        save("chain_row_index", idx.astype(np.float64))
+        save("chain_rows", c2f(rows))
+        return
+    counts = work.d_cnt.download((F,), np.int32)
+    dets = work.d_dets.download((F, DET_CAP, 2), np.int32)
+    az = work.d_az.download((F, DET_CAP), np.int32)
+    el = work.d_el.download((F, DET_CAP), np.int32)
+    n = np.minimum(counts, DET_CAP)
+    save("detect_counts", counts.astype(np.float64))
+    save("detect_dets", np.concatenate([np.concatenate([np.full((k, 1), f), dets[f, :k]], axis=1) for f, k in enumerate(n)])
+         .astype(np.float64).reshape(-1, 3))
+    save("detect_az", np.concatenate([az[f, :k] for f, k in enumerate(n)]).astype(np.float64))
+    save("detect_el", np.concatenate([el[f, :k] for f, k in enumerate(n)]).astype(np.float64))
+    save("detect_frame_index", np.array(picks, np.float64))
+    save("detect_rd_frames", np.stack([c2f(work.d_rd.download((V, S, C), np.complex64, f * CUBE_BYTES)) for f in picks]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -327,10 +372,15 @@ def main():
                          "point-cloud angle argmax (configs[2])")
     ap.add_argument("--detect-path", choices=("fused", "float64"), default="fused",
                     help="detect workload: mmw_detect_points (default) or round 2's mmw_detect_batch + mmw_angle_argmax_exact")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: per-kernel HIP events and rooflines, the "
+                         "in-situ streaming ceiling, the detect sub-records, parity against the oracle, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--no-detect-record", action="store_true",
-                    help="chain workload: skip the `detect` sub-record (BASELINE configs[2] timed after the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events")
+                    help="with --full, chain workload: skip the `detect` sub-records (BASELINE configs[2] timed after the headline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not record per-kernel HIP events")
     ap.add_argument("--profile-every", type=int, default=0,
                     help="record a HIP event pair around every n-th launch of each kernel inside the timed region; 0 = "
                          "auto: every launch when a step is one launch per stage, else every 7th (coprime with the "
@@ -338,6 +388,7 @@ def main():
     _tj = [os.path.join(ROOT, "profiles", n) for n in ("r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json")]
     ap.add_argument("--traffic-json", default=next((t for t in _tj if os.path.exists(t)), _tj[-1]))
     args = ap.parse_args()
+    profiling = args.full and not args.no_profile
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -387,7 +438,7 @@ def main():
         for _ in range(args.warmup if warmup is None else warmup):
             step_fn()
         barrier()
-        if not args.no_profile:
+        if profiling:
             ctx.profile_reset()
             ctx.profile_enable(profile_every)
         t0 = time.perf_counter()
@@ -408,20 +459,22 @@ def main():
 
     elapsed, ev_ms = timed(step, args.profile_every if args.profile_every > 0 else (1 if n_launch == 1 else 7))
     prof = {k: ctx.profile_get(k) for k in ("rd", "angle", "detect", "detect_tail", "detect_exact", "argmax_tail", "argmax_refine", "rd_help", "rd64", "cfar", "compact",
-                                            "plane_l1", "argmax")} if not args.no_profile else {}
+                                            "plane_l1", "argmax")} if profiling else {}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, F, d_out=d_out, work=work)
     # BASELINE configs[2] beside the headline: the detection pipeline on the same resident frames, same K / W
     det_extra = None
-    if not detect and not args.no_detect_record:
+    if args.full and not detect and not args.no_detect_record:
         work = DetectWorkload(ctx, F, args.detect_path)
         # (sub-records: the detection pipeline's rate settles over its first ~20 calls -- 1.99, 1.79, 1.76, 1.74, 1.72 ms per call in
         #  blocks of six, profiles/r04_detect_probe.log -- so they warm up for SUB_WARMUP calls; the headline keeps --warmup)
         det_elapsed, det_ev = timed(lambda: work.step(d_in), 1, max(args.warmup, SUB_WARMUP))
         det_prof = {k: ctx.profile_get(k) for k in ("rd", "detect", "detect_tail", "detect_exact", "argmax_tail", "argmax_refine", "rd_help", "rd64", "cfar", "compact",
-                                                    "plane_l1", "argmax")} if not args.no_profile else {}
+                                                    "plane_l1", "argmax")} if profiling else {}
         det_extra = (det_elapsed, det_ev, det_prof)
         work_os = DetectWorkload(ctx, F, cfar=OS_CFAR)
         os_elapsed, os_ev = timed(lambda: work_os.step(d_in), 1, max(args.warmup, SUB_WARMUP))
-        os_prof = {k: ctx.profile_get(k) for k in ("rd", "rd64", "cfar", "compact", "plane_l1", "argmax")} if not args.no_profile else {}
+        os_prof = {k: ctx.profile_get(k) for k in ("rd", "rd64", "cfar", "compact", "plane_l1", "argmax")} if profiling else {}
         os_extra = (os_elapsed, os_ev, os_prof)
 
     def detect_fields(dt, ev, fam, wl=None):
@@ -505,7 +558,7 @@ def main():
         elif det_extra is not None:
             out["detect"] = detect_fields(*det_extra, wl=work)
             out["detect_os"] = detect_fields(*os_extra, wl=work_os)
-        if not args.no_profile and not detect:
+        if profiling and not detect:
             ang_ms, ang_n = prof["angle"]
             rd_ms, rd_n = prof["rd"]
             if ang_n:
@@ -536,32 +589,34 @@ def main():
                 out["rd_kernel"] = {"avg_launch_us": avg_s * 1e6, "launches": rd_n,
                                     "achieved_GBs": fpl * rd_bytes / avg_s / 1e9,
                                     "algorithmic_bytes_per_launch": fpl * rd_bytes}
-        # parity of this very run: first frame, a frame inside the last full launch and the batch's last frame (the
-        # short tail launch), against the oracle on the SAME bytes -- not timed
-        picks = sorted({0, max(0, (n_launch - 1) * plan["frames_per_launch_max"] - 1) if not detect else F // 2, F - 1})
-        if detect:
-            out["parity"], total_dets = work.parity(d_in, picks)
-            out["detections_per_frame"] = total_dets / F
-            parity_ok = all(v["detection_indices_identical"] and not v["argmax_index_differences"] for v in out["parity"].values())
-        else:
-            saved = [(f"frame{f}", d_in.download((V, S, C), np.complex64, f * CUBE_BYTES),
-                      d_out.download((A, S, C), np.complex64, f * OUT_BYTES)) for f in picks]
-            if "roofline" in out:
-                out["roofline"]["insitu_streaming_ceiling"] = insitu_ceiling(ctx, d_out, F * OUT_BYTES)
-            out["parity_max_rel_err"] = parity_check(saved)
-            parity_ok = max(out["parity_max_rel_err"].values()) <= 1e-5
-            if det_extra is not None:       # detections and argmax bins of three frames of the detect run against the oracle
-                dpar, total_dets = work.parity(d_in, sorted({0, F // 2, F - 1}))
-                out["detect"]["parity"] = dpar
-                out["detect"]["detections_per_frame"] = total_dets / F
-                parity_ok = parity_ok and all(v["detection_indices_identical"] and not v["argmax_index_differences"]
-                                              for v in dpar.values())
-                opar, os_dets = work_os.parity(d_in, sorted({0, F // 2, F - 1}))
-                out["detect_os"]["parity"] = opar
-                out["detect_os"]["detections_per_frame"] = os_dets / F
-                parity_ok = parity_ok and all(v["detection_indices_identical"] and not v["argmax_index_differences"]
-                                              for v in opar.values())
-        if world == 1 and not args.no_cpu_baseline:
+        parity_ok = True
+        if args.full:
+            # parity of this very run: first frame, a frame inside the last full launch and the batch's last frame (the
+            # short tail launch), against the oracle on the SAME bytes -- not timed
+            picks = sorted({0, max(0, (n_launch - 1) * plan["frames_per_launch_max"] - 1) if not detect else F // 2, F - 1})
+            if detect:
+                out["parity"], total_dets = work.parity(d_in, picks)
+                out["detections_per_frame"] = total_dets / F
+                parity_ok = all(v["detection_indices_identical"] and not v["argmax_index_differences"] for v in out["parity"].values())
+            else:
+                saved = [(f"frame{f}", d_in.download((V, S, C), np.complex64, f * CUBE_BYTES),
+                          d_out.download((A, S, C), np.complex64, f * OUT_BYTES)) for f in picks]
+                if "roofline" in out:
+                    out["roofline"]["insitu_streaming_ceiling"] = insitu_ceiling(ctx, d_out, F * OUT_BYTES)
+                out["parity_max_rel_err"] = parity_check(saved)
+                parity_ok = max(out["parity_max_rel_err"].values()) <= 1e-5
+                if det_extra is not None:       # detections and argmax bins of three frames of the detect run against the oracle
+                    dpar, total_dets = work.parity(d_in, sorted({0, F // 2, F - 1}))
+                    out["detect"]["parity"] = dpar
+                    out["detect"]["detections_per_frame"] = total_dets / F
+                    parity_ok = parity_ok and all(v["detection_indices_identical"] and not v["argmax_index_differences"]
+                                                  for v in dpar.values())
+                    opar, os_dets = work_os.parity(d_in, sorted({0, F // 2, F - 1}))
+                    out["detect_os"]["parity"] = opar
+                    out["detect_os"]["detections_per_frame"] = os_dets / F
+                    parity_ok = parity_ok and all(v["detection_indices_identical"] and not v["argmax_index_differences"]
+                                                  for v in opar.values())
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_detect() if detect else cpu_baseline()
             if not detect:
                 out["cpu_baseline_all_cores"] = cpu_baseline_pool()

@@ -31,7 +31,7 @@ def main():
             env[k] = v
         t0 = time.time()
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup",
-                            str(args.warmup), "--frames", str(args.frames), "--no-cpu-baseline"],
+                            str(args.warmup), "--frames", str(args.frames), "--full", "--no-cpu-baseline"],
                            env=env, capture_output=True, text=True, timeout=600)
         line = p.stdout.strip().splitlines()[-1] if p.stdout.strip() else ""
         try:
