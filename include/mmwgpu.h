@@ -51,7 +51,7 @@ typedef struct mmw_ctx mmw_ctx;
 const char *mmw_version(void);
 /* Bumped whenever an exported signature changes: a binding checks it at load (the argtypes of a ctypes binding are
  * hard-coded, so a library of another revision would reinterpret ints as device pointers). */
-#define MMWGPU_ABI_VERSION 5
+#define MMWGPU_ABI_VERSION 6
 int mmw_abi_version(void);
 const char *mmw_last_error(void);
 int mmw_device_count(int *count);
@@ -221,6 +221,32 @@ int mmw_cfar1d(mmw_ctx *ctx, const double *d_x, double *d_thr, double *d_noise, 
                int n_rows, int L, int kind, int num_train, int num_guard, double scale, int k_rank);
 int mmw_compact2d(mmw_ctx *ctx, const uint8_t *d_mask, int32_t *d_dets, int32_t *d_counts,
                   int n_frames, int R, int D, int cap);
+
+/* Batched RangeDopplerGroundDetector (range_doppler_detection/range_doppler_ground_detector.py:72-127 per frame; the
+ * Altimeter's state -- one scalar gate -- stays on the host, everything it gates is computed here for F frames at once).
+ * mmw_ground_candidates: d_profile[F][S] float64 = the chirp-0 range profile of mmw_range_profile_f64, then
+ *   RangeProcessor.find_peaks(20 log10(profile), bins, max_peaks=3) (processors/altimeter.py:79-96 -> range_resp.py:104-149,
+ *   scipy.signal.find_peaks(prominence=6), `>= max - 20`, strongest first) on the device: d_cand[F][3] = d_bins[peak],
+ *   d_counts[F] = number of candidates, or -1 when the frame holds a decision within the picker's rounding band (the host
+ *   then runs find_peaks on d_profile[f]).  S <= 3072.
+ * mmw_ground_zoom_candidates: for every candidate c < d_counts[f] of every frame, Altimeter._look_zoom's window
+ *   [max(1e-6, c - half_width_m), min(hi_cap_m, c + half_width_m)] (hi_cap_m = max(range_bins) - 1e-6) on S bins:
+ *   d_spec[F][3][S] float64 = mean over antennas of |DFT| of hann(S) * chirp 0 at those ranges (RangeProcessor.zoom_fft,
+ *   range_resp.py:59-102, which the reference evaluates with scipy's float64 ZoomFFT; fs = 1 / range_res_m), then the same
+ *   picker with max_peaks=2: d_zcand[F][3][2] = np.linspace(lo, hi, S)[peak], d_zcounts[F][3] (0 past d_counts[f], -1:
+ *   flagged, the host runs find_peaks on d_spec[f][c]).  S <= 2048.
+ * mmw_cfar1d_gated: the 1-D CFAR of mmw_cfar1d (bit-identical decisions) along Doppler on the rows d_gate[f] = (near, far),
+ *   both included, of each frame's d_mag64[F][R][D] (the reference's per-row vel_detector.detect, :110-120), then the ordered
+ *   compaction of mmw_compact2d into d_dets[F][cap][2] / d_counts[F] (exact counts on overflow).  d_mask[F][R][D] is work
+ *   space.  Context option MMW_GROUND_FLAG_ALL = 1: both candidate entries flag every frame / window (tests of the host path). */
+int mmw_ground_candidates(mmw_ctx *ctx, const void *d_cubes, const double *d_bins, double *d_profile, double *d_cand,
+                          int32_t *d_counts, int n_frames, int V, int S, int C);
+int mmw_ground_zoom_candidates(mmw_ctx *ctx, const void *d_cubes, const double *d_cand, const int32_t *d_counts,
+                               double *d_spec, double *d_zcand, int32_t *d_zcounts, int n_frames, int V, int S, int C,
+                               double half_width_m, double hi_cap_m, double fs, double range_max_m);
+int mmw_cfar1d_gated(mmw_ctx *ctx, const double *d_mag64, const int32_t *d_gate, uint8_t *d_mask, int32_t *d_dets,
+                     int32_t *d_counts, int n_frames, int R, int D, int kind, int num_train, int num_guard, double scale,
+                     int k_rank, int cap);
 
 /* mmw_detect_batch: the detection pipeline of RangeDopplerDetector2D for a batch of frames in one call:
  *   d_rd[F][V][S][C] c64 (mmw_range_doppler) and, for antenna 0, d_mag64[F][S][C] -> 2-D CFAR mask -> ordered

@@ -13,6 +13,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from .detectors.base import BaseCFAR1D
 from .detectors.ca_cfar import CaCFAR2D
 from .processors.range_angle_resp import angle_tables
 
@@ -57,16 +58,56 @@ def run_sharded(process_range: Callable[[int, int], Sequence], n_frames: int, di
     return gather_frames(process_range(lo, hi), n_frames, dist)
 
 
+def _check_ground(ground, shape: Tuple[int, int, int]) -> None:
+    """What the batched ground path serves: a RangeDopplerGroundDetector whose velocity detector is a stock 1-D CFAR."""
+    from .processors.range_doppler_detection.range_doppler_ground_detector import RangeDopplerGroundDetector
+    if not isinstance(ground, RangeDopplerGroundDetector):
+        raise ValueError(f"ground= takes a RangeDopplerGroundDetector, got {type(ground).__name__}")
+    vel = ground.vel_detector
+    if not isinstance(vel, BaseCFAR1D):
+        raise ValueError(f"ground=: the velocity detector {type(vel).__name__} is not a 1-D CFAR (a 2-D registry key); "
+                         "the batched ground path runs the stock 1-D detectors only -- use the per-frame API")
+    if type(vel)._compute_thresholds is not BaseCFAR1D._compute_thresholds or \
+            vel.kind not in (_lib.CFAR_CA, _lib.CFAR_OS, _lib.CFAR_GO, _lib.CFAR_SO):
+        raise ValueError(f"ground=: the velocity detector {type(vel).__name__} computes its own thresholds; the batched "
+                         "ground path runs the stock CA / OS / GO / SO 1-D detectors only -- use the per-frame API")
+    S = shape[1]
+    if len(ground.altimeter.range_bins) != S or len(ground.range_bins) != S:
+        raise ValueError(f"ground=: the detector's range tables do not have {S} bins (config and cube shape disagree)")
+
+
+def ground_gates(range_bins: np.ndarray, altitudes_m: np.ndarray) -> np.ndarray:
+    """``slant_gate`` (range_doppler_ground_detector.py) for every frame at once: int32 ``[F, 2]`` rows (near, far), both
+    included; far < near is an empty gate.  The same float64 operations as the per-frame function, vectorised."""
+    alt = np.asarray(altitudes_m, dtype=np.float64)
+    far_m = np.minimum(range_bins[-1], alt / np.cos(np.deg2rad(60.0)))
+    near = np.abs(range_bins[None, :] - alt[:, None]).argmin(axis=1)
+    far = np.abs(range_bins[None, :] - far_m[:, None]).argmin(axis=1)
+    return np.ascontiguousarray(np.stack([near, far], axis=1), dtype=np.int32)
+
+
 class FramePipeline:
     """``[F, V, S, C]`` complex64 cubes in HBM -> RD cube, detections, point clouds, 3-D FFT cube.
 
     Mirrors ``PointCloudGenerator(RangeDopplerDetector2D(CaCFAR2D/OsCFAR2D))`` and
     ``RangeAngleProcessorDBSEnhanced.compute_3d_windowed_fft`` per frame (reference:
-    processors/point_cloud_generator.py:108-140, range_angle_resp_dbs_enhanced.py:137-198)."""
+    processors/point_cloud_generator.py:108-140, range_angle_resp_dbs_enhanced.py:137-198).
+
+    ``ground=<RangeDopplerGroundDetector>``: ``detect()`` / ``point_clouds()`` are those of
+    ``PointCloudGenerator(detector_type="range_doppler_ground_detector")`` called frame by frame, with the detector's
+    Altimeter carried through the batch (and from call to call, and from chunk to chunk of ``stream()``); ``altitudes``
+    holds its reported altitude after every frame.  The velocity detector must be a stock 1-D CFAR (CA / OS / GO / SO)."""
 
     def __init__(self, config_manager, max_frames: int, shape: Tuple[int, int, int], num_angle_bins: int = 64,
                  cfar=None, az_antenna_idxs=(), el_antenna_idxs=(), shift_az_resp=True, shift_el_resp=False,
-                 det_capacity: int = 2048, ctx: _lib.Context = None):
+                 det_capacity: int = 2048, ctx: _lib.Context = None, ground=None):
+        if ground is not None:
+            if cfar is not None:
+                raise ValueError("FramePipeline: pass either cfar= (2-D detection) or ground= (ground detector), not both")
+            _check_ground(ground, tuple(int(x) for x in shape))
+        self.ground = ground
+        self.altitudes = np.empty(0)
+        self.n_flagged = 0      # frames / zoom windows whose peaks the host picked (ground=...)
         self.cm = config_manager
         self.V, self.S, self.C = (int(x) for x in shape)
         self.A = int(num_angle_bins)
@@ -331,12 +372,93 @@ class FramePipeline:
         self.dets = [dets[f, :counts[f]].astype(np.int64) for f in range(F)]
         return self.dets
 
+    # ------------------------------------------------------------------ ground detector
+    def _ground_picks(self, d_cand, d_cnt, shape, host_pick) -> Tuple[np.ndarray, np.ndarray]:
+        """Candidate table + counts of a device picker; entries it flagged (count -1) are re-picked by ``host_pick(index)``,
+        which returns the candidate ranges RangeProcessor.find_peaks gives on the data the device left behind."""
+        cand = d_cand.download(shape, np.float64).copy()
+        cnt = d_cnt.download(shape[:-1], np.int32).copy()
+        for idx in zip(*(i.tolist() for i in np.nonzero(cnt < 0))):
+            got = host_pick(idx)
+            cand[idx][:len(got)] = got
+            cnt[idx] = len(got)
+            self.n_flagged += 1
+        return cand, cnt
+
+    def _detect_ground(self) -> np.ndarray:
+        """RD (+ L1 norms) and float64 |RD| of antenna 0 for every frame; range-profile peaks (and the zoom peaks around every
+        one of them) on the device; the Altimeter's scan over the frames on the host; the gated Doppler CFAR + ordered
+        compaction on the device.  Returns the detection counts."""
+        F, V, S, C, cap = self.n_frames, self.V, self.S, self.C, self.cap
+        L, h, bufs = self.ctx.lib, self.ctx.handle, self.bufs
+        det = self.ground
+        alt, vel = det.altimeter, det.vel_detector
+        precise = bool(det.altimeter_params.get("precise_est_enabled", True))
+        F1 = max(F, 1)
+        d_mag = bufs.get("mag64", F1 * S * C * 8)
+        d_prof, d_bins = bufs.get("g_profile", F1 * S * 8), bufs.get("g_bins", S * 8)
+        d_cand, d_ccnt = bufs.get("g_cand", F1 * 3 * 8), bufs.get("g_ccount", F1 * 4)
+        d_bins.upload(np.ascontiguousarray(alt.range_bins[:S], dtype=np.float64))
+        self.n_flagged = 0
+        step = 32768
+        for f0 in range(0, F, step):
+            nf = min(step, F - f0)
+            cube = self.d_in.at(f0 * self.cube_bytes)
+            _lib.check(L.mmw_range_doppler(h, cube, self.d_rd.at(f0 * self.cube_bytes), None, nf, V, S, C))
+            _lib.check(L.mmw_plane_l1(h, cube, self.d_l1.at(f0 * V * 4), nf, V, S, C))
+            _lib.check(L.mmw_range_doppler_mag64(h, cube, d_mag.at(f0 * S * C * 8), nf, V, S, C, 0))
+            _lib.check(L.mmw_ground_candidates(h, cube, d_bins.ptr, d_prof.at(f0 * S * 8), d_cand.at(f0 * 24), d_ccnt.at(f0 * 4),
+                                               nf, V, S, C))
+
+        def coarse_pick(idx):
+            prof = d_prof.download((S,), np.float64, idx[0] * S * 8)
+            return alt.find_peaks(20 * np.log10(prof), alt.range_bins, max_peaks=3)[0]
+        cand, ccnt = self._ground_picks(d_cand, d_ccnt, (F, 3), coarse_pick)
+        coarse = [cand[f, :ccnt[f]].tolist() for f in range(F)]
+        fine = None
+        if precise:
+            half = float(alt.zoom_half_width_m)
+            hi_cap = float(alt.range_bins.max()) - 1e-6
+            d_spec = bufs.get("g_spec", F1 * 3 * S * 8)
+            d_zc, d_zcnt = bufs.get("g_zcand", F1 * 6 * 8), bufs.get("g_zcount", F1 * 3 * 4)
+            if self.n_flagged:                              # the host's picks replace the flagged rows
+                d_cand.upload(cand)
+                d_ccnt.upload(ccnt)
+            for f0 in range(0, F, step):
+                nf = min(step, F - f0)
+                _lib.check(L.mmw_ground_zoom_candidates(h, self.d_in.at(f0 * self.cube_bytes), d_cand.at(f0 * 24), d_ccnt.at(f0 * 4),
+                                                        d_spec.at(f0 * 3 * S * 8), d_zc.at(f0 * 48), d_zcnt.at(f0 * 12), nf,
+                                                        V, S, C, half, hi_cap, 1 / self.cm.range_res_m, float(self.cm.range_max_m)))
+
+            def zoom_pick(idx):
+                f, j = idx
+                c = cand[f, j]
+                lo, hi = max(1e-6, c - half), min(hi_cap, c + half)          # Altimeter._look_zoom's window
+                spec = d_spec.download((S,), np.float64, (f * 3 + j) * S * 8)
+                return alt.find_peaks(20 * np.log10(spec), np.linspace(lo, hi, S), max_peaks=2)[0]
+            zc, zcnt = self._ground_picks(d_zc, d_zcnt, (F, 3, 2), zoom_pick)
+            fine = [[zc[f, j, :zcnt[f, j]].tolist() for j in range(3)] for f in range(F)]
+        self._scan_inputs = (coarse, fine)                  # (kept for tools/ground_batch_probe.py's timing of the scan)
+        self.altitudes = np.array(alt.lock.advance(coarse, fine), dtype=np.float64)
+        d_gate = bufs.get("g_gate", F1 * 8)
+        d_gate.upload(ground_gates(det.range_bins, self.altitudes))
+        d_mask = bufs.get("mask", F1 * S * C)
+        for f0 in range(0, F, step):
+            nf = min(step, F - f0)
+            _lib.check(L.mmw_cfar1d_gated(h, d_mag.at(f0 * S * C * 8), d_gate.at(f0 * 8), d_mask.at(f0 * S * C),
+                                          self.d_dets.at(f0 * cap * 8), self.d_cnt.at(f0 * 4), nf, S, C, int(vel.kind),
+                                          int(vel.num_train), int(vel.num_guard), float(vel._scale()), int(vel._k_rank()), cap))
+        return self.d_cnt.download((F,), np.int32)
+
     def detect(self) -> List[np.ndarray]:
         """RD (all antennas, fp32) + CFAR on antenna 0 + ordered compaction for every frame.
 
-        Returns the per-frame int64 ``(N, 2)`` [range_idx, doppler_idx] arrays (row-major order, == np.where)."""
+        Returns the per-frame int64 ``(N, 2)`` [range_idx, doppler_idx] arrays (row-major order, == np.where).  With
+        ``ground=``: the ground detector's detections (gated rows, Doppler CFAR), and ``altitudes`` is set."""
         F = self.n_frames
         self._alloc_detect()
+        if self.ground is not None:
+            return self._fetch_dets(self._detect_ground())
         if self._fused_supported(False):
             return self._fetch_dets(self._detect_fused(False))
         for f0 in range(0, F, 32768):       # grid limits of the per-frame launches
@@ -356,7 +478,7 @@ class FramePipeline:
         self.n_refined = 0      # detections re-evaluated in float64 (near-ties of the float32 pass)
         F, cap = self.n_frames, self.cap
         self._alloc_detect()
-        if self._fused_supported(True):
+        if self.ground is None and self._fused_supported(True):
             dets = self._fetch_dets(self._detect_fused(True))
             az_idx = self.d_az.download((F, cap), np.int32) if self.az else None
             el_idx = self.d_el.download((F, cap), np.int32) if self.el else None
@@ -388,12 +510,18 @@ class MultiDeviceFramePipeline:
     (scripts/test_vel_estimation.py:145-151) turn into on a multi-GPU node; ``bench.py --gpus N`` keeps the
     one-process-per-GPU form.
 
+    The ground detector (``FramePipeline(ground=...)``) is refused: its Altimeter carries an altitude track from each frame
+    to the next, which a split by frames would break.
+
     ``part_factory(device, max_frames)`` builds the per-device pipeline (default: ``FramePipeline`` on a new
     ``Context(device)``); tests inject a host-only fake to exercise the split / join logic without a GPU."""
 
     def __init__(self, config_manager, max_frames: int, shape: Tuple[int, int, int], devices: Optional[Sequence[int]] = None,
                  part_factory: Optional[Callable[[int, int], object]] = None, **pipeline_kwargs):
         from concurrent.futures import ThreadPoolExecutor
+        if pipeline_kwargs.get("ground") is not None:
+            raise ValueError("MultiDeviceFramePipeline cannot take ground=: the altitude track runs through the frames in "
+                             "order, so it cannot be split across devices -- use one FramePipeline(ground=...)")
         if devices is None:
             devices = list(range(_lib.device_count()))
         self.devices = [int(d) for d in devices]

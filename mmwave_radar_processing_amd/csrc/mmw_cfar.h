@@ -623,11 +623,9 @@ struct Cfar1dArgs {
     int k_rank;
 };
 
-__global__ __launch_bounds__(256) void k_cfar1d(Cfar1dArgs p) {
-    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= (long)p.n_rows * p.L) return;
-    const int i = (int)(gid % p.L);
-    const double *x = p.x + (gid - i);
+// Threshold of cell i of the row x (length p.L) and its noise estimate: +inf / 0 outside the valid region.  Shared by
+// k_cfar1d and the gated Doppler CFAR of the ground pipeline (mmw_ground.h), so both decide bit-identically.
+__device__ __forceinline__ double cfar1d_threshold(const Cfar1dArgs &p, const double *x, int i, double *est_out) {
     const int half = p.T + p.G;
     double thr = INFINITY, est = 0.0;
     if (i >= half && i < p.L - half) {
@@ -647,6 +645,17 @@ __global__ __launch_bounds__(256) void k_cfar1d(Cfar1dArgs p) {
         }
         thr = p.scale * est;
     }
+    *est_out = est;
+    return thr;
+}
+
+__global__ __launch_bounds__(256) void k_cfar1d(Cfar1dArgs p) {
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (long)p.n_rows * p.L) return;
+    const int i = (int)(gid % p.L);
+    const double *x = p.x + (gid - i);
+    double est;
+    const double thr = cfar1d_threshold(p, x, i, &est);
     if (p.thr) p.thr[gid] = thr;
     if (p.noise) p.noise[gid] = est;
     if (p.mask) p.mask[gid] = (x[i] > thr) ? 1 : 0;

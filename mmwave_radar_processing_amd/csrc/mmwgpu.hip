@@ -2,6 +2,7 @@
 #include "mmw_ctx.h"
 #include "mmw_launch.h"
 #include "mmw_cfar.h"
+#include "mmw_ground.h"
 #include "mmw_misc.h"
 #include "mmw_czt.h"
 #include "mmw_beamform.h"
@@ -1550,6 +1551,65 @@ int mmw_detect_batch(mmw_ctx *ctx, const void *d_cubes, void *d_rd, double *d_ma
     MMW_TRY(cfar2d_impl(ctx, d_mag64, nullptr, nullptr, d_mask, n_frames, S, C, cfar_kind, train_r, train_d, guard_r,
                         guard_d, scale, k_rank));
     return compact2d_impl(ctx, d_mask, d_dets, d_counts, n_frames, S, C, cap);
+}
+
+// ------------------------------------------------------------------ batched ground detector (mmw_ground.h)
+static int ground_flag_all(const mmw_ctx *ctx) { return opt_int(ctx, "MMW_GROUND_FLAG_ALL", 0) != 0 ? 1 : 0; }
+
+int mmw_ground_candidates(mmw_ctx *ctx, const void *d_cubes, const double *d_bins, double *d_profile, double *d_cand,
+                          int32_t *d_counts, int n_frames, int V, int S, int C) {
+    MMW_REQUIRE(ctx && d_cubes && d_bins && d_profile && d_cand && d_counts, "null argument");
+    MMW_JOIN(ctx);
+    MMW_REQUIRE(n_frames >= 0 && n_frames <= 65535 && V > 0 && S >= 3 && C > 0, "bad shape");
+    MMW_REQUIRE((size_t)S * 2 * sizeof(double) <= 48 * 1024, "range profile of %d samples does not fit the picker's LDS", S);
+    if (n_frames == 0) return MMW_OK;
+    MMW_TRY(range_profile_impl<double>(ctx, d_cubes, d_profile, n_frames, V, S, C, 0));
+    ProfScope ps(ctx, "ground");
+    hipLaunchKernelGGL(k_ground_peaks, dim3(n_frames), dim3(256), (size_t)S * 2 * sizeof(double), ctx->stream, d_profile, d_bins,
+                       d_cand, d_counts, S, ground_flag_all(ctx));
+    return check_launch("ground_peaks");
+}
+
+int mmw_ground_zoom_candidates(mmw_ctx *ctx, const void *d_cubes, const double *d_cand, const int32_t *d_counts, double *d_spec,
+                               double *d_zcand, int32_t *d_zcounts, int n_frames, int V, int S, int C, double half_width_m,
+                               double hi_cap_m, double fs, double range_max_m) {
+    MMW_REQUIRE(ctx && d_cubes && d_cand && d_counts && d_spec && d_zcand && d_zcounts, "null argument");
+    MMW_JOIN(ctx);
+    MMW_REQUIRE(n_frames >= 0 && n_frames <= 65535 && V > 0 && S >= 3 && C > 0, "bad shape");
+    MMW_REQUIRE(S <= 256 * ZOOM_BINS_PER_THREAD, "zoom window of %d bins: at most %d", S, 256 * ZOOM_BINS_PER_THREAD);
+    MMW_REQUIRE(half_width_m > 0.0 && fs > 0.0 && range_max_m > 0.0, "bad zoom window parameters");
+    if (n_frames == 0) return MMW_OK;
+    const void *hann;
+    MMW_TRY(get_table<double>(ctx, TAB_HANN, S, &hann));
+    const int vb = std::max(1, std::min(std::min(V, ZOOM_VB), (int)((48 * 1024) / ((size_t)S * sizeof(double2)))));
+    const size_t lds = std::max((size_t)vb * S * sizeof(double2), (size_t)S * 2 * sizeof(double));
+    ZoomArgs a{(const float2 *)d_cubes, (const double *)hann, d_cand, d_counts, d_spec, d_zcand, d_zcounts, V, S, C, vb,
+               half_width_m, hi_cap_m, fs, range_max_m, ground_flag_all(ctx)};
+    ProfScope ps(ctx, "ground");
+    hipLaunchKernelGGL(k_ground_zoom, dim3(GROUND_COARSE, n_frames), dim3(256), lds, ctx->stream, a);
+    return check_launch("ground_zoom");
+}
+
+int mmw_cfar1d_gated(mmw_ctx *ctx, const double *d_mag64, const int32_t *d_gate, uint8_t *d_mask, int32_t *d_dets,
+                     int32_t *d_counts, int n_frames, int R, int D, int kind, int num_train, int num_guard, double scale,
+                     int k_rank, int cap) {
+    MMW_REQUIRE(ctx && d_mag64 && d_gate && d_mask && d_dets && d_counts, "null argument");
+    MMW_JOIN(ctx);
+    MMW_REQUIRE(n_frames >= 0 && n_frames <= 65535 && R > 0 && D > 0 && cap >= 0 && num_train >= 0 && num_guard >= 0,
+                "bad shape");
+    MMW_REQUIRE(kind >= MMW_CFAR_CA && kind <= MMW_CFAR_SO, "unknown CFAR kind %d", kind);
+    MMW_REQUIRE(num_train <= 512, "num_train too large for the exact summation order");
+    if (kind == MMW_CFAR_OS)
+        MMW_REQUIRE(k_rank >= 1 && k_rank <= 2 * num_train, "k_rank must be between 1 and %d, got %d", 2 * num_train, k_rank);
+    if (n_frames == 0) return MMW_OK;
+    Cfar1dArgs a{d_mag64, nullptr, nullptr, nullptr, 0, D, kind, num_train, num_guard, scale, k_rank};
+    {
+        ProfScope ps(ctx, "cfar");
+        hipLaunchKernelGGL(k_cfar1d_gated, dim3((unsigned)(((long)R * D + 255) / 256), n_frames), dim3(256), 0, ctx->stream, a,
+                           d_gate, d_mask, R);
+        MMW_TRY(check_launch("cfar1d_gated"));
+    }
+    return compact2d_impl(ctx, d_mask, d_dets, d_counts, n_frames, R, D, cap);
 }
 
 // ------------------------------------------------------------------ point cloud

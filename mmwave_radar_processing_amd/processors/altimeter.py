@@ -8,15 +8,18 @@ infrastructure).  Here the tracker is a small state machine:
   two altitudes the callers read;
 * a frame is a list of *look stages* -- coarse profile, then optionally a zoom around the coarse hit -- each turning the
   cube into candidate ranges on the device (float64 range profile / chirp-z zoom) + one scipy peak pick on the host;
-* every stage's candidates pass through ``GroundLock.admit``; the first stage with no admissible candidate ends the frame
-  with the previous altitude, the last stage's hit is accepted.
+* ``GroundLock.step`` is the one statement of the rules: the coarse candidates pass the gate, the zoom around the admitted
+  one (if any) passes it again; no admissible candidate at a stage ends the frame with the previous altitude, the last
+  stage's hit is accepted.  ``GroundLock.advance`` runs the same step over a sequence of frames whose candidate lists were
+  computed beforehand (the zoom candidates of EVERY coarse candidate): that is how ``batch.FramePipeline(ground=...)``
+  tracks F frames after one batched device pass, on plain floats.
 
-STATEFUL: one instance per frame sequence, not part of the batch API.
+STATEFUL: one instance per frame sequence; the batch pipeline carries this lock from call to call.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Callable, List, Optional
+from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 
@@ -35,11 +38,45 @@ class GroundLock:
     def __post_init__(self):
         self.measured_m = self.reported_m = self.floor_m
 
-    def admit(self, candidates_m: np.ndarray) -> Optional[float]:
+    def pick(self, candidates_m: Sequence[float]) -> Optional[int]:
+        """Position of the nearest candidate inside the gate (the first of equal ones), or None.  Plain float arithmetic:
+        the same IEEE operations as the NumPy expression of the reference, without its per-call overhead."""
+        floor, last, reach = self.floor_m, self.measured_m, self.reach_m
+        best = None
+        for i, c in enumerate(candidates_m):
+            if c >= floor and abs(c - last) <= reach and (best is None or c < candidates_m[best]):
+                best = i
+        return best
+
+    def admit(self, candidates_m) -> Optional[float]:
         """The nearest candidate inside the gate, or None."""
-        c = np.asarray(candidates_m, dtype=float)
-        inside = c[(c >= self.floor_m) & (np.abs(c - self.measured_m) <= self.reach_m)]
-        return float(inside.min()) if inside.size else None
+        c = [float(x) for x in np.ravel(candidates_m)]
+        i = self.pick(c)
+        return None if i is None else c[i]
+
+    def step(self, coarse_m: Sequence[float], refine: Optional[Callable[[int], Sequence[float]]] = None) -> float:
+        """One frame: the admitted coarse candidate, then (``refine`` given: the precise mode) the admitted one of
+        ``refine(position of that coarse candidate)``; the last hit is accepted.  Returns the reported altitude."""
+        i = self.pick(coarse_m)
+        if i is None:
+            return self.reported_m
+        hit = coarse_m[i]
+        if refine is not None:
+            fine = refine(i)
+            j = self.pick(fine)
+            if j is None:
+                return self.reported_m
+            hit = fine[j]
+        self.accept(float(hit))
+        return self.reported_m
+
+    def advance(self, coarse_per_frame: Sequence[Sequence[float]],
+                fine_per_frame: Optional[Sequence[Sequence[Sequence[float]]]] = None) -> List[float]:
+        """``step`` over a frame sequence whose candidates are known up front: ``fine_per_frame[f][i]`` is the zoom
+        candidate list around ``coarse_per_frame[f][i]``.  Returns the reported altitude after every frame."""
+        if fine_per_frame is None:
+            return [self.step(coarse) for coarse in coarse_per_frame]
+        return [self.step(coarse, fine.__getitem__) for coarse, fine in zip(coarse_per_frame, fine_per_frame)]
 
     def accept(self, range_m: float) -> None:
         self.measured_m = range_m
@@ -91,11 +128,6 @@ class Altimeter(RangeProcessor):
         return self.find_peaks(20 * np.log10(spectrum), bins, max_peaks=2)[0]
 
     def process(self, adc_cube: np.ndarray, precise_est_enabled: bool = True, **kwargs) -> float:
-        stages: List[Callable] = [self._look_coarse] + ([self._look_zoom] if precise_est_enabled else [])
-        hit = None
-        for look in stages:
-            hit = self.lock.admit(look(adc_cube, hit))
-            if hit is None:
-                return self.lock.reported_m
-        self.lock.accept(hit)
-        return self.lock.reported_m
+        coarse = self._look_coarse(adc_cube, None).tolist()
+        refine = (lambda i: self._look_zoom(adc_cube, coarse[i]).tolist()) if precise_est_enabled else None
+        return self.lock.step(coarse, refine)

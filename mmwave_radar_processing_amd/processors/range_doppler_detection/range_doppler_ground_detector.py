@@ -3,8 +3,9 @@ runs on |RD| of antenna 0 in every gated row
 (reference: .../range_doppler_detection/range_doppler_ground_detector.py:13-127; the default ``detector_type`` of the
 reference's frame-loop scripts, scripts/test_vel_estimation.py:134).
 
-STATEFUL through its Altimeter (last-altitude gate): single-frame API only, one instance per frame sequence; it is not part
-of ``batch.FramePipeline``."""
+STATEFUL through its Altimeter (last-altitude gate): one instance per frame sequence.  Frame by frame here; for F frames
+resident on the device, ``batch.FramePipeline(ground=<this detector>)`` computes the same detections and altitude track
+(and leaves this detector's Altimeter where the frame loop would), with the stock 1-D velocity detectors."""
 from __future__ import annotations
 
 from typing import Dict
@@ -26,7 +27,7 @@ def slant_gate(range_bins: np.ndarray, altitude_m: float, max_off_nadir_deg: flo
     return np.arange(near, far + 1)
 
 
-@rd_detector("range_doppler_ground_detector")       # stateful (Altimeter): single-frame API only
+@rd_detector("range_doppler_ground_detector")       # stateful (Altimeter); batched by FramePipeline(ground=...)
 class RangeDopplerGroundDetector(RangeDopplerDetector):
     def __init__(self, config_manager, vel_cfar_type: str = "os_cfar_1d", vel_cfar_params: Dict = {},
                  altimeter_params: Dict = {}, **kwargs):
