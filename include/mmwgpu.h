@@ -51,7 +51,7 @@ typedef struct mmw_ctx mmw_ctx;
 const char *mmw_version(void);
 /* Bumped whenever an exported signature changes: a binding checks it at load (the argtypes of a ctypes binding are
  * hard-coded, so a library of another revision would reinterpret ints as device pointers). */
-#define MMWGPU_ABI_VERSION 6
+#define MMWGPU_ABI_VERSION 7
 int mmw_abi_version(void);
 const char *mmw_last_error(void);
 int mmw_device_count(int *count);
@@ -247,6 +247,35 @@ int mmw_ground_zoom_candidates(mmw_ctx *ctx, const void *d_cubes, const double *
 int mmw_cfar1d_gated(mmw_ctx *ctx, const double *d_mag64, const int32_t *d_gate, uint8_t *d_mask, int32_t *d_dets,
                      int32_t *d_counts, int n_frames, int R, int D, int kind, int num_train, int num_guard, double scale,
                      int k_rank, int cap);
+
+/* Batched RangeDopplerDetectorSequential (range_doppler_detection/range_doppler_detector_sequential.py:72-107 per frame;
+ * the detector has no state across frames).  All CFAR arguments are those of mmw_cfar1d, decisions bit-identical to it.
+ * mmw_seq_rows: the range CFAR (rng_detector.detect(range_resp), :84-88) on d_profile[F][S] float64, the chirp-0 range
+ *   profiles of mmw_range_profile_f64: d_rows[F][S] int32 holds, per frame, the selected range rows in ascending order in
+ *   its first d_nrows[f] entries.  One launch, no host round trip.  S <= 3072.
+ * mmw_seq_detect: for every frame and every selected row r the float64 Doppler row of virtual antenna 0,
+ *   |fftshift_C FFT_C(hann(C)[c] X[r, c])| with X[r, c] = sum_s hann(S)[s] x[0, s, c] exp(-2 pi i r s / S) (the values of
+ *   mmw_range_doppler_mag64: range_doppler_resp.py:98-103 and range_doppler_detector.py:78, up to the rounding of a direct
+ *   sum against an FFT), the velocity CFAR on it (vel_detector.detect per row, :95-101) and the hits in the order of the
+ *   reference's nested comprehension (rows ascending, Doppler ascending == np.where) in d_dets[F][cap][2] / d_counts[F];
+ *   counts are exact when a frame overflows cap.  d_cubes is the [F][V][S][C] complex64 batch.  Neither a float64 plane
+ *   nor a mask is written.  d_rowmag is NULL, or (to measure the rows against an oracle) [F][S][C] float64 space in which
+ *   entry [f][j] receives the Doppler row of range bin d_rows[f][j].  MMW_ERR_UNSUPPORTED (nothing launched) when mmw_seq_route(ctx, S, C) != 0 for the shape alone:
+ *   the kernel needs 16 (S + C) + 25 * 4 * max(C, 256) bytes of LDS, at most 160 KiB (S <= 3072 with any C <= 512).
+ * mmw_seq_detect_plane: the same result by the plain route: mmw_range_doppler_mag64 of antenna 0 into d_mag64[F][S][C], the
+ *   kernel of mmw_cfar1d_gated on the listed rows (d_mask[F][S][C] is work space), mmw_compact2d.
+ * mmw_seq_route: 0 when FramePipeline(sequential=...) should call mmw_seq_detect, 1 for mmw_seq_detect_plane: the
+ *   context option MMW_SEQ_FULL_PLANE (default 1: the full plane measured faster; 0 asks for the row
+ *   kernel) or a shape the row kernel does not serve.  ctx may be NULL (environment and default only). */
+int mmw_seq_rows(mmw_ctx *ctx, const double *d_profile, int32_t *d_rows, int32_t *d_nrows, int n_frames, int S, int kind,
+                 int num_train, int num_guard, double scale, int k_rank);
+int mmw_seq_detect(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_rows, const int32_t *d_nrows, int32_t *d_dets,
+                   int32_t *d_counts, int n_frames, int V, int S, int C, int kind, int num_train, int num_guard, double scale,
+                   int k_rank, int cap, double *d_rowmag);
+int mmw_seq_detect_plane(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_rows, const int32_t *d_nrows, double *d_mag64,
+                         uint8_t *d_mask, int32_t *d_dets, int32_t *d_counts, int n_frames, int V, int S, int C, int kind,
+                         int num_train, int num_guard, double scale, int k_rank, int cap);
+int mmw_seq_route(mmw_ctx *ctx, int S, int C);
 
 /* mmw_detect_batch: the detection pipeline of RangeDopplerDetector2D for a batch of frames in one call:
  *   d_rd[F][V][S][C] c64 (mmw_range_doppler) and, for antenna 0, d_mag64[F][S][C] -> 2-D CFAR mask -> ordered

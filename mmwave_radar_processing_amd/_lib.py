@@ -22,7 +22,7 @@ MMW_ERR_INVALID = -1
 MMW_ERR_TRUNCATED = -4
 MMW_ERR_UNSUPPORTED = -5
 RESULT_POOL_CAP = 1 << 30       # bytes of pinned result blocks the default context may hold (handed out + pooled)
-ABI_VERSION = 6          # include/mmwgpu.h MMWGPU_ABI_VERSION: the argtypes below are for exactly this revision
+ABI_VERSION = 7          # include/mmwgpu.h MMWGPU_ABI_VERSION: the argtypes below are for exactly this revision
 CFAR_CA, CFAR_OS, CFAR_GO, CFAR_SO = 0, 1, 2, 3
 ANGLE_MAGNITUDE, ANGLE_NO_WINDOW, ANGLE_NO_SHIFT = 1, 2, 4
 QUEUE_COMPUTE, QUEUE_COPY = 0, 1
@@ -87,6 +87,10 @@ _SIGNATURES = {
     "mmw_ground_candidates": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i],
     "mmw_ground_zoom_candidates": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d],
     "mmw_cfar1d_gated": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _i],
+    "mmw_seq_rows": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i],
+    "mmw_seq_detect": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _vp],
+    "mmw_seq_detect_plane": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i],
+    "mmw_seq_route": [_vp, _i, _i],
     "mmw_detect_points_supported": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i],
     "mmw_detect_points": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i,
                           _ip, _i, _i, _ip, _i, _i, _i, _ip],

@@ -58,22 +58,39 @@ def run_sharded(process_range: Callable[[int, int], Sequence], n_frames: int, di
     return gather_frames(process_range(lo, hi), n_frames, dist)
 
 
+def _check_stock_cfar1d(kw: str, role: str, det) -> None:
+    """A batched path runs ``det`` through ``cfar1d_threshold`` on the device, so it must be one of the stock 1-D CFARs."""
+    if not isinstance(det, BaseCFAR1D):
+        raise ValueError(f"{kw}=: the {role} detector {type(det).__name__} is not a 1-D CFAR (a 2-D registry key); "
+                         f"the batched {kw} path runs the stock 1-D detectors only -- use the per-frame API")
+    if type(det)._compute_thresholds is not BaseCFAR1D._compute_thresholds or \
+            det.kind not in (_lib.CFAR_CA, _lib.CFAR_OS, _lib.CFAR_GO, _lib.CFAR_SO):
+        raise ValueError(f"{kw}=: the {role} detector {type(det).__name__} computes its own thresholds; the batched "
+                         f"{kw} path runs the stock CA / OS / GO / SO 1-D detectors only -- use the per-frame API")
+
+
 def _check_ground(ground, shape: Tuple[int, int, int]) -> None:
     """What the batched ground path serves: a RangeDopplerGroundDetector whose velocity detector is a stock 1-D CFAR."""
     from .processors.range_doppler_detection.range_doppler_ground_detector import RangeDopplerGroundDetector
     if not isinstance(ground, RangeDopplerGroundDetector):
         raise ValueError(f"ground= takes a RangeDopplerGroundDetector, got {type(ground).__name__}")
-    vel = ground.vel_detector
-    if not isinstance(vel, BaseCFAR1D):
-        raise ValueError(f"ground=: the velocity detector {type(vel).__name__} is not a 1-D CFAR (a 2-D registry key); "
-                         "the batched ground path runs the stock 1-D detectors only -- use the per-frame API")
-    if type(vel)._compute_thresholds is not BaseCFAR1D._compute_thresholds or \
-            vel.kind not in (_lib.CFAR_CA, _lib.CFAR_OS, _lib.CFAR_GO, _lib.CFAR_SO):
-        raise ValueError(f"ground=: the velocity detector {type(vel).__name__} computes its own thresholds; the batched "
-                         "ground path runs the stock CA / OS / GO / SO 1-D detectors only -- use the per-frame API")
+    _check_stock_cfar1d("ground", "velocity", ground.vel_detector)
     S = shape[1]
     if len(ground.altimeter.range_bins) != S or len(ground.range_bins) != S:
         raise ValueError(f"ground=: the detector's range tables do not have {S} bins (config and cube shape disagree)")
+
+
+def _check_sequential(sequential) -> None:
+    """What the batched sequential path serves: a RangeDopplerDetectorSequential whose two detectors are stock 1-D CFARs."""
+    from .processors.range_doppler_detection.range_doppler_detector_sequential import RangeDopplerDetectorSequential
+    if not isinstance(sequential, RangeDopplerDetectorSequential):
+        raise ValueError(f"sequential= takes a RangeDopplerDetectorSequential, got {type(sequential).__name__}")
+    _check_stock_cfar1d("sequential", "range", sequential.rng_detector)
+    _check_stock_cfar1d("sequential", "velocity", sequential.vel_detector)
+
+
+def _cfar1d_args(det) -> Tuple[int, int, int, float, int]:
+    return int(det.kind), int(det.num_train), int(det.num_guard), float(det._scale()), int(det._k_rank())
 
 
 def ground_gates(range_bins: np.ndarray, altitudes_m: np.ndarray) -> np.ndarray:
@@ -96,16 +113,26 @@ class FramePipeline:
     ``ground=<RangeDopplerGroundDetector>``: ``detect()`` / ``point_clouds()`` are those of
     ``PointCloudGenerator(detector_type="range_doppler_ground_detector")`` called frame by frame, with the detector's
     Altimeter carried through the batch (and from call to call, and from chunk to chunk of ``stream()``); ``altitudes``
-    holds its reported altitude after every frame.  The velocity detector must be a stock 1-D CFAR (CA / OS / GO / SO)."""
+    holds its reported altitude after every frame.  The velocity detector must be a stock 1-D CFAR (CA / OS / GO / SO).
+
+    ``sequential=<RangeDopplerDetectorSequential>``: ``detect()`` / ``point_clouds()`` are those of
+    ``PointCloudGenerator(detector_type="range_doppler_detector_sequential")`` called frame by frame.  Only the two CFAR
+    parameter sets of the detector are read (both stock 1-D CFARs); its per-frame caches are not touched."""
 
     def __init__(self, config_manager, max_frames: int, shape: Tuple[int, int, int], num_angle_bins: int = 64,
                  cfar=None, az_antenna_idxs=(), el_antenna_idxs=(), shift_az_resp=True, shift_el_resp=False,
-                 det_capacity: int = 2048, ctx: _lib.Context = None, ground=None):
+                 det_capacity: int = 2048, ctx: _lib.Context = None, ground=None, sequential=None):
         if ground is not None:
             if cfar is not None:
                 raise ValueError("FramePipeline: pass either cfar= (2-D detection) or ground= (ground detector), not both")
             _check_ground(ground, tuple(int(x) for x in shape))
+        if sequential is not None:
+            if cfar is not None or ground is not None:
+                raise ValueError("FramePipeline: pass one of cfar= (2-D detection), ground= (ground detector) and "
+                                 "sequential= (sequential detector), not several")
+            _check_sequential(sequential)
         self.ground = ground
+        self.sequential = sequential
         self.altitudes = np.empty(0)
         self.n_flagged = 0      # frames / zoom windows whose peaks the host picked (ground=...)
         self.cm = config_manager
@@ -450,15 +477,52 @@ class FramePipeline:
                                           int(vel.num_train), int(vel.num_guard), float(vel._scale()), int(vel._k_rank()), cap))
         return self.d_cnt.download((F,), np.int32)
 
+    # ------------------------------------------------------------------ sequential detector
+    def _detect_sequential(self, with_rd: bool) -> np.ndarray:
+        """Float64 chirp-0 range profiles -> range CFAR -> row lists (``mmw_seq_rows``), then the Doppler rows of the listed
+        range bins, the velocity CFAR and the ordered hits in one kernel (``mmw_seq_detect``; ``mmw_seq_detect_plane`` when
+        ``mmw_seq_route`` says so).  ``with_rd``: also the float32 RD cube and the plane norms the exact argmax reads
+        (``point_clouds()``); ``detect()`` alone needs neither and skips both.  Returns the detection counts."""
+        F, V, S, C, cap = self.n_frames, self.V, self.S, self.C, self.cap
+        L, h, bufs = self.ctx.lib, self.ctx.handle, self.bufs
+        rng, vel = _cfar1d_args(self.sequential.rng_detector), _cfar1d_args(self.sequential.vel_detector)
+        F1 = max(F, 1)
+        d_prof = bufs.get("s_profile", F1 * S * 8)
+        d_rows, d_nrows = bufs.get("s_rows", F1 * S * 4), bufs.get("s_nrows", F1 * 4)
+        plane = bool(L.mmw_seq_route(h, S, C))
+        if plane:
+            d_mag, d_mask = bufs.get("mag64", F1 * S * C * 8), bufs.get("mask", F1 * S * C)
+        step = 32768                        # grid limits of the per-frame launches
+        for f0 in range(0, F, step):
+            nf = min(step, F - f0)
+            cube = self.d_in.at(f0 * self.cube_bytes)
+            if with_rd:
+                _lib.check(L.mmw_range_doppler(h, cube, self.d_rd.at(f0 * self.cube_bytes), None, nf, V, S, C))
+                _lib.check(L.mmw_plane_l1(h, cube, self.d_l1.at(f0 * V * 4), nf, V, S, C))
+            _lib.check(L.mmw_range_profile_f64(h, cube, d_prof.at(f0 * S * 8), nf, V, S, C, 0))
+            rows, nrows = d_rows.at(f0 * S * 4), d_nrows.at(f0 * 4)
+            _lib.check(L.mmw_seq_rows(h, d_prof.at(f0 * S * 8), rows, nrows, nf, S, *rng))
+            dets, cnt = self.d_dets.at(f0 * cap * 8), self.d_cnt.at(f0 * 4)
+            if plane:
+                _lib.check(L.mmw_seq_detect_plane(h, cube, rows, nrows, d_mag.at(f0 * S * C * 8), d_mask.at(f0 * S * C), dets, cnt,
+                                                  nf, V, S, C, *vel, cap))
+            else:
+                _lib.check(L.mmw_seq_detect(h, cube, rows, nrows, dets, cnt, nf, V, S, C, *vel, cap, None))
+        return self.d_cnt.download((F,), np.int32)
+
     def detect(self) -> List[np.ndarray]:
         """RD (all antennas, fp32) + CFAR on antenna 0 + ordered compaction for every frame.
 
         Returns the per-frame int64 ``(N, 2)`` [range_idx, doppler_idx] arrays (row-major order, == np.where).  With
-        ``ground=``: the ground detector's detections (gated rows, Doppler CFAR), and ``altitudes`` is set."""
+        ``ground=``: the ground detector's detections (gated rows, Doppler CFAR), and ``altitudes`` is set.  With
+        ``sequential=``: the sequential detector's detections; the float32 RD cube is not computed (``point_clouds()``
+        computes it for the argmax)."""
         F = self.n_frames
         self._alloc_detect()
         if self.ground is not None:
             return self._fetch_dets(self._detect_ground())
+        if self.sequential is not None:
+            return self._fetch_dets(self._detect_sequential(False))
         if self._fused_supported(False):
             return self._fetch_dets(self._detect_fused(False))
         for f0 in range(0, F, 32768):       # grid limits of the per-frame launches
@@ -478,12 +542,12 @@ class FramePipeline:
         self.n_refined = 0      # detections re-evaluated in float64 (near-ties of the float32 pass)
         F, cap = self.n_frames, self.cap
         self._alloc_detect()
-        if self.ground is None and self._fused_supported(True):
+        if self.ground is None and self.sequential is None and self._fused_supported(True):
             dets = self._fetch_dets(self._detect_fused(True))
             az_idx = self.d_az.download((F, cap), np.int32) if self.az else None
             el_idx = self.d_el.download((F, cap), np.int32) if self.el else None
         else:
-            dets = self.detect()
+            dets = self._fetch_dets(self._detect_sequential(True)) if self.sequential is not None else self.detect()
             az_idx = self._argmax(self.az, self.shift_az, "az_idx") if self.az else None
             el_idx = self._argmax(self.el, self.shift_el, "el_idx") if self.el else None
         out = []
@@ -511,7 +575,7 @@ class MultiDeviceFramePipeline:
     one-process-per-GPU form.
 
     The ground detector (``FramePipeline(ground=...)``) is refused: its Altimeter carries an altitude track from each frame
-    to the next, which a split by frames would break.
+    to the next, which a split by frames would break.  ``sequential=`` has no state across frames and shards like ``cfar=``.
 
     ``part_factory(device, max_frames)`` builds the per-device pipeline (default: ``FramePipeline`` on a new
     ``Context(device)``); tests inject a host-only fake to exercise the split / join logic without a GPU."""

@@ -6,7 +6,8 @@
 //   k_ground_zoom       one workgroup per (frame, coarse candidate): Altimeter._look_zoom's window around the candidate,
 //                       the mean-over-antennas |DFT| of chirp 0 on S bins in float64, then the same picker (2 peaks)
 //   k_cfar1d_gated      the Doppler CFAR (cfar1d_threshold, the code of k_cfar1d) on the rows near..far of each frame's
-//                       float64 |RD| plane; k_compact2d then lists the hits in row-major order
+//                       float64 |RD| plane (or on a list of rows: the sequential detector's full-plane route); k_compact2d
+//                       then lists the hits in row-major order
 //
 // The picker decides every comparison scipy makes on 20 log10(p) -- neighbours and plateaus, the prominence bases, the
 // 6-dB prominence, the `>= max - 20` cut, the final ordering -- from the device's own 20 log10(p).  Device (OCML) and host
@@ -215,15 +216,30 @@ __global__ __launch_bounds__(256) void k_ground_zoom(ZoomArgs a) {
     if (threadIdx.x == 0) a.zcounts[w] = a.flag_all ? -1 : n;
 }
 
-// mask[f][r][d] = the 1-D CFAR decision of Doppler bin d in range row r when gate[f] = (near, far) holds r, else 0
-__global__ __launch_bounds__(256) void k_cfar1d_gated(Cfar1dArgs p, const int32_t *gate, uint8_t *mask, int R) {
+// mask[f][r][d] = the 1-D CFAR decision of Doppler bin d in range row r when row r of frame f is selected, else 0.
+// Selected rows: gate[f] = (near, far), both included (rows == nullptr: the ground detector), or the ascending list
+// rows[f][0 .. nrows[f]) of R-entry lists (the sequential detector's full-plane route, mmw_seq.h).
+__global__ __launch_bounds__(256) void k_cfar1d_gated(Cfar1dArgs p, const int32_t *gate, const int32_t *rows, const int32_t *nrows,
+                                                      uint8_t *mask, int R) {
     const long cell = (long)blockIdx.x * 256 + threadIdx.x;
     const long f = blockIdx.y;
     if (cell >= (long)R * p.L) return;
     const int r = (int)(cell / p.L), d = (int)(cell - (long)r * p.L);
-    const int near = gate[2 * f], far = gate[2 * f + 1];
+    bool selected;
+    if (rows == nullptr) {
+        selected = r >= gate[2 * f] && r <= gate[2 * f + 1];
+    } else {
+        const int32_t *list = rows + f * R;
+        int lo = 0, hi = nrows[f] < R ? nrows[f] : R;                // first entry >= r
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (list[mid] < r) lo = mid + 1;
+            else hi = mid;
+        }
+        selected = lo < (nrows[f] < R ? nrows[f] : R) && list[lo] == r;
+    }
     uint8_t hit = 0;
-    if (r >= near && r <= far) {
+    if (selected) {
         const double *x = p.x + (f * R + r) * (long)p.L;
         double est;
         hit = x[d] > cfar1d_threshold(p, x, d, &est) ? 1 : 0;

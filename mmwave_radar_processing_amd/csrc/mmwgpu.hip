@@ -3,6 +3,7 @@
 #include "mmw_launch.h"
 #include "mmw_cfar.h"
 #include "mmw_ground.h"
+#include "mmw_seq.h"
 #include "mmw_misc.h"
 #include "mmw_czt.h"
 #include "mmw_beamform.h"
@@ -1606,10 +1607,99 @@ int mmw_cfar1d_gated(mmw_ctx *ctx, const double *d_mag64, const int32_t *d_gate,
     {
         ProfScope ps(ctx, "cfar");
         hipLaunchKernelGGL(k_cfar1d_gated, dim3((unsigned)(((long)R * D + 255) / 256), n_frames), dim3(256), 0, ctx->stream, a,
-                           d_gate, d_mask, R);
+                           d_gate, (const int32_t *)nullptr, (const int32_t *)nullptr, d_mask, R);
         MMW_TRY(check_launch("cfar1d_gated"));
     }
     return compact2d_impl(ctx, d_mask, d_dets, d_counts, n_frames, R, D, cap);
+}
+
+// ------------------------------------------------------------------ batched sequential detector (mmw_seq.h)
+static int cfar1d_args_ok(int kind, int num_train, int num_guard, int k_rank) {
+    MMW_REQUIRE(num_train >= 0 && num_guard >= 0, "bad CFAR window");
+    MMW_REQUIRE(kind >= MMW_CFAR_CA && kind <= MMW_CFAR_SO, "unknown CFAR kind %d", kind);
+    MMW_REQUIRE(num_train <= 512, "num_train too large for the exact summation order");
+    if (kind == MMW_CFAR_OS)
+        MMW_REQUIRE(k_rank >= 1 && k_rank <= 2 * num_train, "k_rank must be between 1 and %d, got %d", 2 * num_train, k_rank);
+    return MMW_OK;
+}
+
+int mmw_seq_route(mmw_ctx *ctx, int S, int C) {
+    if (opt_int(ctx, "MMW_SEQ_FULL_PLANE", SEQ_FULL_PLANE_DEFAULT) != 0) return 1;
+    return (S > 0 && C > 0 && seq_lds_bytes(S, C) <= SEQ_LDS_MAX) ? 0 : 1;
+}
+
+int mmw_seq_rows(mmw_ctx *ctx, const double *d_profile, int32_t *d_rows, int32_t *d_nrows, int n_frames, int S, int kind,
+                 int num_train, int num_guard, double scale, int k_rank) {
+    MMW_REQUIRE(ctx && d_profile && d_rows && d_nrows, "null argument");
+    MMW_JOIN(ctx);
+    MMW_REQUIRE(n_frames >= 0 && n_frames <= 65535 && S > 0, "bad shape");
+    MMW_REQUIRE((size_t)S * 2 * sizeof(double) <= 48 * 1024, "range profile of %d samples does not fit the row picker's LDS", S);
+    MMW_TRY(cfar1d_args_ok(kind, num_train, num_guard, k_rank));
+    if (n_frames == 0) return MMW_OK;
+    Cfar1dArgs a{d_profile, nullptr, nullptr, nullptr, n_frames, S, kind, num_train, num_guard, scale, k_rank};
+    ProfScope ps(ctx, "seq");
+    hipLaunchKernelGGL(k_seq_rows, dim3(n_frames), dim3(256), (size_t)S * (sizeof(double) + 1), ctx->stream, a, d_rows, d_nrows);
+    return check_launch("seq_rows");
+}
+
+int mmw_seq_detect(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_rows, const int32_t *d_nrows, int32_t *d_dets,
+                   int32_t *d_counts, int n_frames, int V, int S, int C, int kind, int num_train, int num_guard, double scale,
+                   int k_rank, int cap, double *d_rowmag) {
+    MMW_REQUIRE(ctx && d_cubes && d_rows && d_nrows && d_dets && d_counts, "null argument");
+    MMW_JOIN(ctx);
+    MMW_REQUIRE(n_frames >= 0 && n_frames <= 65535 && V > 0 && S > 0 && C > 0 && cap >= 0, "bad shape");
+    MMW_TRY(cfar1d_args_ok(kind, num_train, num_guard, k_rank));
+    const size_t lds = seq_lds_bytes(S, C);
+    if (lds > SEQ_LDS_MAX)
+        return set_error(MMW_ERR_UNSUPPORTED, "sequential row kernel: %d x %d needs %zu bytes of LDS (mmw_seq_route says so): "
+                         "use mmw_seq_detect_plane", S, C, lds);
+    if (n_frames == 0) return MMW_OK;
+    SeqArgs a{};
+    a.cubes = (const float2 *)d_cubes;
+    const void *t;
+    MMW_TRY(get_table<double>(ctx, TAB_HANN, S, &t));
+    a.hann_s = (const double *)t;
+    MMW_TRY(get_table<double>(ctx, TAB_HANN, C, &t));
+    a.hann_c = (const double *)t;
+    MMW_TRY(get_table<double>(ctx, TAB_TWIDDLE, S, &t));
+    a.tw_s = (const double2 *)t;
+    MMW_TRY(get_table<double>(ctx, TAB_TWIDDLE, C, &t));
+    a.tw_c = (const double2 *)t;
+    a.rows = d_rows;
+    a.nrows = d_nrows;
+    a.dets = d_dets;
+    a.counts = d_counts;
+    a.rowmag = d_rowmag;
+    a.V = V;
+    a.S = S;
+    a.C = C;
+    a.cap = cap;
+    a.cfar = Cfar1dArgs{nullptr, nullptr, nullptr, nullptr, 0, C, kind, num_train, num_guard, scale, k_rank};
+    if (lds > 64 * 1024)
+        MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_seq_detect), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds));         // per device, so on every call
+    ProfScope ps(ctx, "seq");
+    hipLaunchKernelGGL(k_seq_detect, dim3(n_frames), dim3(256), lds, ctx->stream, a);
+    return check_launch("seq_detect");
+}
+
+int mmw_seq_detect_plane(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_rows, const int32_t *d_nrows, double *d_mag64,
+                         uint8_t *d_mask, int32_t *d_dets, int32_t *d_counts, int n_frames, int V, int S, int C, int kind,
+                         int num_train, int num_guard, double scale, int k_rank, int cap) {
+    MMW_REQUIRE(ctx && d_cubes && d_rows && d_nrows && d_mag64 && d_mask && d_dets && d_counts, "null argument");
+    MMW_JOIN(ctx);
+    MMW_REQUIRE(n_frames >= 0 && n_frames <= 65535 && V > 0 && S > 0 && C > 0 && cap >= 0, "bad shape");
+    MMW_TRY(cfar1d_args_ok(kind, num_train, num_guard, k_rank));
+    if (n_frames == 0) return MMW_OK;
+    MMW_TRY(range_doppler_mag64_impl(ctx, d_cubes, d_mag64, n_frames, V, S, C, 0));
+    Cfar1dArgs a{d_mag64, nullptr, nullptr, nullptr, 0, C, kind, num_train, num_guard, scale, k_rank};
+    {
+        ProfScope ps(ctx, "cfar");
+        hipLaunchKernelGGL(k_cfar1d_gated, dim3((unsigned)(((long)S * C + 255) / 256), n_frames), dim3(256), 0, ctx->stream, a,
+                           (const int32_t *)nullptr, d_rows, d_nrows, d_mask, S);
+        MMW_TRY(check_launch("cfar1d_rows"));
+    }
+    return compact2d_impl(ctx, d_mask, d_dets, d_counts, n_frames, S, C, cap);
 }
 
 // ------------------------------------------------------------------ point cloud
