@@ -4,12 +4,17 @@
 // the training-cell sums are accumulated in the ORDER NumPy uses for the reference's expressions
 // (probed against numpy 2.2.6 in the build container; the pairwise kernel is unchanged since 1.x):
 //   CaCFAR2D (detectors/ca_cfar.py:134-136)  np.sum(windows*mask, axis=(2,3)):
-//       per window row an 8-accumulator pairwise sum over Wd entries (masked entries are +0.0),
-//       rows added sequentially, then / N.
+//       per window row an 8-accumulator pairwise sum over Wd entries (a masked entry is x * 0.0: +-0.0 for a finite
+//       cell, NaN for an infinite or NaN one, as the reference's product has it), rows added sequentially, then / N.
+//       A plane with ONE valid column (D == Wd) is the exception: NumPy then reduces each window as one contiguous
+//       run, a pairwise sum over all Wr * Wd products (k_cfar2d_ca_1col).
 //   CaCFAR1D (ca_cfar.py:51-54)  np.mean(windows[:, mask], axis=1): the fancy-indexed copy is
-//       F-ordered, so the reduction is a plain left-to-right sum over [left cells, right cells], / N.
-//   Go/SoCFAR1D (go_so_cfar.py:43-55)  np.mean over contiguous views: pairwise sum per side, / num_train.
-//   OsCFAR (os_cfar.py:68-73,176-177)  np.partition(...)[k-1] == the k-th smallest: exact selection.
+//       F-ordered, so the reduction is a plain left-to-right sum over [left cells, right cells], / N.  A row with ONE
+//       window (L == 2 (T + G) + 1) is the exception: a pairwise sum over the 2 T cells.
+//   Go/SoCFAR1D (go_so_cfar.py:43-55)  np.mean over contiguous views: pairwise sum per side, / num_train; np.maximum /
+//       np.minimum hand a NaN on from either side.
+//   OsCFAR (os_cfar.py:68-73,176-177)  np.partition(...)[k-1] == the k-th smallest: exact selection, every NaN
+//       (whatever its sign bit) ranking above +inf as in NumPy's sort order.
 // Decision rule X > T strict; outside the valid region T = +inf, noise = 0 (ca_cfar.py:96-97,144-153).
 #pragma once
 #include "mmw_ctx.h"
@@ -43,23 +48,74 @@ template <int DEPTH, typename G> __device__ double np_pairwise(G get, int lo, in
     return 0.0;
 }
 
-// order-preserving key of a double (total order, negatives included)
-__device__ __forceinline__ unsigned long long f64_key(double v) {
+// NumPy's pairwise_sum for any n: the same recursion on an explicit stack (a block of n > 128 splits at n / 2 rounded
+// down to a multiple of 8).  For the rare single-window reductions, whose run is the whole window.
+template <typename G> __device__ double np_pairwise_any(G get, int n) {
+    int lo_s[32], n_s[32], phase[32];
+    double left[32];
+    int sp = 0;
+    lo_s[0] = 0, n_s[0] = n, phase[0] = 0;
+    double ret = 0.0;
+    while (sp >= 0) {
+        if (phase[sp] == 0) {
+            if (n_s[sp] <= 128) {
+                ret = np_pairwise<0>(get, lo_s[sp], n_s[sp]);
+                --sp;
+            } else {
+                int n2 = n_s[sp] / 2;
+                n2 -= n2 % 8;
+                phase[sp] = 1;
+                lo_s[sp + 1] = lo_s[sp], n_s[sp + 1] = n2, phase[sp + 1] = 0;
+                ++sp;
+            }
+        } else if (phase[sp] == 1) {
+            int n2 = n_s[sp] / 2;
+            n2 -= n2 % 8;
+            left[sp] = ret;
+            phase[sp] = 2;
+            lo_s[sp + 1] = lo_s[sp] + n2, n_s[sp + 1] = n_s[sp] - n2, phase[sp + 1] = 0;
+            ++sp;
+        } else {
+            ret = left[sp] + ret;
+            --sp;
+        }
+    }
+    return ret;
+}
+
+// order-preserving key of a double (total order, negatives included); a NaN whose sign bit is set sorts below -inf
+__device__ __forceinline__ unsigned long long f64_key_raw(double v) {
     unsigned long long u = (unsigned long long)__double_as_longlong(v);
     return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+// The key the sorts use: every NaN, whatever its sign bit and payload, gets the key of the canonical quiet NaN -- above
+// +inf, where np.partition puts NaNs, and below the padding key ~0.
+__device__ __forceinline__ unsigned long long f64_key(double v) {
+    return (v != v) ? 0xFFF8000000000000ull : f64_key_raw(v);
 }
 __device__ __forceinline__ double f64_unkey(unsigned long long k) {
     unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
     return __longlong_as_double((long long)u);
 }
 
-// k-th smallest (1-based) of the values get(0..n) by bitwise bisection on the ordered key.
+// k-th smallest (1-based) of the values get(0..n) by bitwise bisection on the ordered key, NaNs ranking last as in
+// np.partition: a NaN when fewer than k values are numbers; otherwise the NaNs with the sign bit set (x86's inf - inf),
+// which the raw key puts first, shift the rank by their number.  One counting pass beside the 64 of the bisection.
 template <typename G> __device__ double kth_smallest(G get, int n, int k) {
+    int n_nan = 0, n_neg_nan = 0;
+    for (int i = 0; i < n; ++i) {
+        const double v = get(i);
+        const bool is_nan = v != v;
+        n_nan += is_nan ? 1 : 0;
+        n_neg_nan += (is_nan && __double_as_longlong(v) < 0) ? 1 : 0;
+    }
+    if (k > n - n_nan) return __longlong_as_double(0x7FF8000000000000ll);
+    k += n_neg_nan;
     unsigned long long prefix = 0;
     for (int bit = 63; bit >= 0; --bit) {
         const unsigned long long cand = prefix | (1ull << bit);
         int below = 0;
-        for (int i = 0; i < n; ++i) below += (f64_key(get(i)) < cand) ? 1 : 0;
+        for (int i = 0; i < n; ++i) below += (f64_key_raw(get(i)) < cand) ? 1 : 0;
         if (below < k) prefix = cand;
     }
     return f64_unkey(prefix);
@@ -197,13 +253,13 @@ __global__ __launch_bounds__(CFAR_TR *CFAR_TC) void k_cfar2d(Cfar2dArgs p) {
             double sf, sm;
             if (Wd > 128) {                               // rare: generic pairwise recursion
                 sf = np_pairwise<2>([&](int wd) { return src[wd]; }, 0, Wd);
-                sm = np_pairwise<2>([&](int wd) { return (wd >= z0 && wd <= z1) ? 0.0 : src[wd]; }, 0, Wd);
+                sm = np_pairwise<2>([&](int wd) { return (wd >= z0 && wd <= z1) ? src[wd] * 0.0 : src[wd]; }, 0, Wd);
             } else if (Wd < 8) {
                 sf = sm = 0.0;
                 for (int i = 0; i < Wd; ++i) {
                     const double v = src[i];
                     sf += v;
-                    sm += (i >= z0 && i <= z1) ? 0.0 : v;
+                    sm += (i >= z0 && i <= z1) ? v * 0.0 : v;
                 }
             } else {                                      // NumPy's 8-accumulator block, both sums in one sweep
                 double f[8], m[8];
@@ -211,7 +267,7 @@ __global__ __launch_bounds__(CFAR_TR *CFAR_TC) void k_cfar2d(Cfar2dArgs p) {
                 for (int j = 0; j < 8; ++j) {
                     const double v = src[j];
                     f[j] = v;
-                    m[j] = (j >= z0 && j <= z1) ? 0.0 : v;
+                    m[j] = (j >= z0 && j <= z1) ? v * 0.0 : v;
                 }
                 int i = 8;
                 for (; i < Wd - (Wd % 8); i += 8) {
@@ -219,7 +275,7 @@ __global__ __launch_bounds__(CFAR_TR *CFAR_TC) void k_cfar2d(Cfar2dArgs p) {
                     for (int j = 0; j < 8; ++j) {
                         const double v = src[i + j];
                         f[j] += v;
-                        m[j] += (i + j >= z0 && i + j <= z1) ? 0.0 : v;
+                        m[j] += (i + j >= z0 && i + j <= z1) ? v * 0.0 : v;
                     }
                 }
                 sf = ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
@@ -227,7 +283,7 @@ __global__ __launch_bounds__(CFAR_TR *CFAR_TC) void k_cfar2d(Cfar2dArgs p) {
                 for (; i < Wd; ++i) {
                     const double v = src[i];
                     sf += v;
-                    sm += (i >= z0 && i <= z1) ? 0.0 : v;
+                    sm += (i >= z0 && i <= z1) ? v * 0.0 : v;
                 }
             }
             rs_full[t] = sf;
@@ -436,13 +492,13 @@ __global__ __launch_bounds__(256) void k_cfar2d_ca(Cfar2dArgs p) {
         double sf, sm;
         if (Wd > 128) {                               // rare: generic pairwise recursion
             sf = np_pairwise<2>([&](int wd) { return src[wd]; }, 0, Wd);
-            sm = np_pairwise<2>([&](int wd) { return (wd >= z0 && wd <= z1) ? 0.0 : src[wd]; }, 0, Wd);
+            sm = np_pairwise<2>([&](int wd) { return (wd >= z0 && wd <= z1) ? src[wd] * 0.0 : src[wd]; }, 0, Wd);
         } else if (Wd < 8) {
             sf = sm = 0.0;
             for (int i = 0; i < Wd; ++i) {
                 const double v = src[i];
                 sf += v;
-                sm += (i >= z0 && i <= z1) ? 0.0 : v;
+                sm += (i >= z0 && i <= z1) ? v * 0.0 : v;
             }
         } else {                                      // NumPy's 8-accumulator block, both sums in one sweep
             double f[8], m[8];
@@ -450,7 +506,7 @@ __global__ __launch_bounds__(256) void k_cfar2d_ca(Cfar2dArgs p) {
             for (int j = 0; j < 8; ++j) {
                 const double v = src[j];
                 f[j] = v;
-                m[j] = (j >= z0 && j <= z1) ? 0.0 : v;
+                m[j] = (j >= z0 && j <= z1) ? v * 0.0 : v;
             }
             int i = 8;
             for (; i < Wd - (Wd % 8); i += 8) {
@@ -458,7 +514,7 @@ __global__ __launch_bounds__(256) void k_cfar2d_ca(Cfar2dArgs p) {
                 for (int j = 0; j < 8; ++j) {
                     const double v = src[i + j];
                     f[j] += v;
-                    m[j] += (i + j >= z0 && i + j <= z1) ? 0.0 : v;
+                    m[j] += (i + j >= z0 && i + j <= z1) ? v * 0.0 : v;
                 }
             }
             sf = ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
@@ -466,7 +522,7 @@ __global__ __launch_bounds__(256) void k_cfar2d_ca(Cfar2dArgs p) {
             for (; i < Wd; ++i) {
                 const double v = src[i];
                 sf += v;
-                sm += (i >= z0 && i <= z1) ? 0.0 : v;
+                sm += (i >= z0 && i <= z1) ? v * 0.0 : v;
             }
         }
         rs_full[t] = sf;
@@ -493,6 +549,34 @@ __global__ __launch_bounds__(256) void k_cfar2d_ca(Cfar2dArgs p) {
         if (p.noise) p.noise[o] = est;
         if (p.mask) p.mask[o] = (tile[(lr + hr) * TW + lc + hd] > thr) ? 1 : 0;
     }
+}
+
+// CA-CFAR 2-D on a plane exactly one window wide (D == Wd: the valid region is the single column hd).  np.sum over the
+// last two axes of the reference's [R - Wr + 1][1][Wr][Wd] product then runs over each window as ONE contiguous run of
+// Wr * Wd values -- NumPy's pairwise sum of the whole window, not row sums added in order.  One thread per cell, straight
+// from global memory: a handful of valid cells per frame, no tile worth staging.
+__global__ __launch_bounds__(256) void k_cfar2d_ca_1col(Cfar2dArgs p) {
+    const long plane = (long)p.R * p.D;
+    const long cell = (long)blockIdx.x * 256 + threadIdx.x;
+    if (cell >= plane) return;
+    const double *X = p.X + (long)blockIdx.y * plane;
+    const int hr = p.tr + p.gr, hd = p.td + p.gd, Wr = 2 * hr + 1, Wd = 2 * hd + 1;
+    const int r = (int)(cell / p.D), c = (int)(cell - (long)r * p.D);
+    double thr = INFINITY, est = 0.0;
+    if (c == hd && r >= hr && r < p.R - hr) {
+        const double *win = X + (long)(r - hr) * p.D;             // the window's rows are whole plane rows
+        const double sum = np_pairwise_any([&](int i) {
+            const int wr = i / Wd, wd = i - wr * Wd;
+            const bool guard = wr >= p.tr && wr <= p.tr + 2 * p.gr && wd >= p.td && wd <= p.td + 2 * p.gd;
+            return guard ? win[i] * 0.0 : win[i];
+        }, Wr * Wd);
+        est = sum / (double)(Wr * Wd - (2 * p.gr + 1) * (2 * p.gd + 1));
+        thr = p.scale * est;
+    }
+    const long o = (long)blockIdx.y * plane + cell;
+    if (p.thr) p.thr[o] = thr;
+    if (p.noise) p.noise[o] = est;
+    if (p.mask) p.mask[o] = (X[cell] > thr) ? 1 : 0;
 }
 
 // OS-CFAR when only the detection mask is wanted (mmw_detect_batch, FramePipeline): no selection at all.
@@ -633,15 +717,20 @@ __device__ __forceinline__ double cfar1d_threshold(const Cfar1dArgs &p, const do
         const int rs = p.T + 2 * p.G + 1;            // start of the right training cells
         if (p.kind == MMW_CFAR_CA) {
             double s = 0.0;
-            for (int q = 0; q < p.T; ++q) s += w[q];
-            for (int q = 0; q < p.T; ++q) s += w[rs + q];
+            if (p.L == 2 * half + 1) {               // one window: NumPy reduces its 2 T cells as one contiguous run
+                s = np_pairwise<3>([&](int q) { return q < p.T ? w[q] : w[rs + q - p.T]; }, 0, 2 * p.T);
+            } else {
+                for (int q = 0; q < p.T; ++q) s += w[q];
+                for (int q = 0; q < p.T; ++q) s += w[rs + q];
+            }
             est = s / (double)(2 * p.T);
         } else if (p.kind == MMW_CFAR_OS) {
             est = kth_smallest([&](int q) { return q < p.T ? w[q] : w[rs + q - p.T]; }, 2 * p.T, p.k_rank);
         } else {
             const double ml = np_pairwise<2>([&](int q) { return w[q]; }, 0, p.T) / (double)p.T;
             const double mr = np_pairwise<2>([&](int q) { return w[rs + q]; }, 0, p.T) / (double)p.T;
-            est = (p.kind == MMW_CFAR_GO) ? fmax(ml, mr) : fmin(ml, mr);
+            // np.maximum / np.minimum hand a NaN on; fmax / fmin would drop it
+            est = (ml != ml || mr != mr) ? ml + mr : (p.kind == MMW_CFAR_GO) ? fmax(ml, mr) : fmin(ml, mr);
         }
         thr = p.scale * est;
     }

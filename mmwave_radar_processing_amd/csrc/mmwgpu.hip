@@ -1462,6 +1462,15 @@ static int cfar2d_impl(mmw_ctx *ctx, const double *d_X, double *d_thr, double *d
         }
     }
     MMW_REQUIRE(2 * hd + 1 <= 512, "Doppler window too wide for the exact summation order");
+    if (kind == MMW_CFAR_CA && D == 2 * hd + 1 && R >= 2 * hr + 1) {
+        // one valid column: NumPy sums each window as one run (k_cfar2d_ca_1col)
+        MMW_REQUIRE((long)(2 * hr + 1) * (2 * hd + 1) <= 0x7fffffffL, "CFAR window too large");
+        if (n_frames == 0) return MMW_OK;
+        ProfScope ps(ctx, "cfar");
+        Cfar2dArgs a{d_X, d_thr, d_noise, d_mask, R, D, kind, train_r, train_d, guard_r, guard_d, scale, k_rank, 0};
+        hipLaunchKernelGGL(k_cfar2d_ca_1col, dim3((unsigned)(((long)R * D + 255) / 256), n_frames), dim3(256), 0, ctx->stream, a);
+        return check_launch("cfar2d_ca_1col");
+    }
     if (kind == MMW_CFAR_CA) {
         // 32 x 32 tile (k_cfar2d_ca) while tile + halo + row-sum tables fit the default LDS limit
         const size_t th = CA_TR + 2 * hr, tw = CA_TC + 2 * hd;

@@ -1,0 +1,269 @@
+"""CFAR decision kernels straight through the C ABI on ties, non-finite cells and every dispatch route.
+
+Inputs and references: tests/cfar_cases.py (tests/test_cfar_cases_host.py asserts, without a GPU, that the inputs hold
+cells that EQUAL their threshold and windows whose order statistic is a NaN / finite beside a NaN / +inf).  Every 2-D
+case runs mmw_cfar2d twice on F = 4 frames (quantised, constant, ramp or its negation, non-finite): with threshold and
+noise buffers (thresholds, noise and mask compared) and with both NULL (the mask-only dispatch; mask compared), then
+mmw_compact2d against np.where.  Arrays are compared with assert_array_equal: NaN equals NaN, +0.0 equals -0.0 (which of
+the two np.partition returns is open), everything else bit for bit.
+
+| kind | train / guard                          | reaches                                                                   |
+|------|----------------------------------------|---------------------------------------------------------------------------|
+| OS   | (5,5)/(3,2), (4,4)/(2,2)               | mask only: k_cfar2d_os_mask_v; with MMW_OS_MASK_FORM=0: k_cfar2d_os_mask;   |
+|      |                                        | with thresholds: k_cfar2d, 1024-element register sort + integral images   |
+| OS   | (2,2)/(1,1), (1,1)/(0,0), (0,3)/(0,1)  | mask only: k_cfar2d_os_mask; with thresholds: k_cfar2d, 512-element sort   |
+| OS   | (8,8)/(2,2)                            | k_cfar2d, tile above 1024 cells: LDS sort + rank bisection                 |
+| OS   | (2,2)/(1,1), scale 0.0 and -1.0        | mask only with a non-positive scale: falls through to k_cfar2d             |
+| CA   | (4,4)/(2,2), (1,1)/(0,0), (2,9)/(1,3)  | k_cfar2d_ca (Wd = 13, Wd < 8, Wd = 25)                                     |
+| CA   | (25,25)/(4,4) on 75 x 67               | CA half of k_cfar2d (k_cfar2d_ca would need 108 KiB of LDS, k_cfar2d 61)   |
+| CA   | (1,62)/(0,2) on 9 x 150                | Wd = 129 in k_cfar2d_ca: the pairwise recursion                            |
+| CA   | (3,60)/(0,4) on 12 x 150,              | Wd = 129 and 261 in k_cfar2d (second recursion level)                      |
+|      | (1,126)/(0,4) on 5 x 300               |                                                                           |
+| CA   | (4,4)/(2,2), (1,62)/(0,2), D == Wd     | k_cfar2d_ca_1col: one valid column, NumPy sums the window as one run       |
+
+1-D (mmw_cfar1d, k_cfar1d -> cfar1d_threshold): all four kinds, (T, G) up to num_train 512, five rows of 1301 cells in
+one call (rows straddle workgroups), rows of exactly one window and one cell short of it.  mmw_cfar1d_gated
+(k_cfar1d_gated + k_compact2d) with the gate over all rows, with and without capacity overflow.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+import cfar_cases as cc
+from mmwave_radar_processing_amd import _lib
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    return _lib.default_context()
+
+
+def run_cfar2d(ctx, planes, kind, train, guard, scale, k, with_thr):
+    F, R, D = planes.shape
+    bufs = [ctx.alloc(planes.nbytes), ctx.alloc(planes.nbytes), ctx.alloc(planes.nbytes), ctx.alloc(F * R * D)]
+    d_x, d_t, d_n, d_m = bufs
+    try:
+        d_x.upload(planes)
+        d_m.upload(np.full((F, R, D), 7, np.uint8))          # every cell must be written
+        _lib.check(ctx.lib.mmw_cfar2d(ctx.handle, d_x.ptr, d_t.ptr if with_thr else None, d_n.ptr if with_thr else None,
+                                      d_m.ptr, F, R, D, kind, train[0], train[1], guard[0], guard[1], float(scale), int(k)))
+        mask = d_m.download((F, R, D), np.uint8)
+        if not with_thr:
+            return None, None, mask
+        return d_t.download((F, R, D), np.float64), d_n.download((F, R, D), np.float64), mask
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def compacted(ctx, mask, cap):
+    F, R, D = mask.shape
+    bufs = [ctx.alloc(mask.nbytes), ctx.alloc(max(1, F * cap * 8)), ctx.alloc(F * 4)]
+    try:
+        bufs[0].upload(mask)
+        _lib.check(ctx.lib.mmw_compact2d(ctx.handle, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, F, R, D, cap))
+        return bufs[1].download((F, cap, 2), np.int32), bufs[2].download((F,), np.int32)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def assert_compaction(dets, counts, mask, cap):
+    for f in range(mask.shape[0]):
+        rows, cols = np.where(mask[f])
+        assert counts[f] == len(rows)
+        n = min(cap, len(rows))
+        np.testing.assert_array_equal(dets[f, :n, 0], rows[:n])
+        np.testing.assert_array_equal(dets[f, :n, 1], cols[:n])
+
+
+def refs_2d(planes, kind, train, guard, scale, k):
+    out = [cc.ref_cfar2d(p, kind, train, guard, scale, k) for p in planes]
+    return tuple(np.stack([o[i] for o in out]) for i in range(3))
+
+
+def check_2d(ctx, planes, kind, train, guard, scale, k=0, full=True, mask_only=True, compact=False):
+    thr_ref, noise_ref, mask_ref = refs_2d(planes, kind, train, guard, scale, k)
+    tag = f"{cc.KIND_NAMES[kind]} {train}/{guard} scale {scale!r} k {k}"
+    if full:
+        thr, noise, mask = run_cfar2d(ctx, planes, kind, train, guard, scale, k, True)
+        np.testing.assert_array_equal(noise, noise_ref, err_msg=tag + " noise")
+        np.testing.assert_array_equal(thr, thr_ref, err_msg=tag + " thresholds")
+        np.testing.assert_array_equal(mask, mask_ref, err_msg=tag + " mask (with thresholds)")
+    if mask_only:
+        mask = run_cfar2d(ctx, planes, kind, train, guard, scale, k, False)[2]
+        np.testing.assert_array_equal(mask, mask_ref, err_msg=tag + " mask (mask only)")
+    if compact:
+        cap = planes.shape[1] * planes.shape[2]
+        dets, counts = compacted(ctx, mask, cap)
+        assert_compaction(dets, counts, mask_ref, cap)
+    return mask_ref
+
+
+@functools.lru_cache(maxsize=None)
+def os_planes(train, guard, negate):
+    half = (train[0] + guard[0], train[1] + guard[1])
+    return cc.planes_2d(cc.os_plane_shape(train, guard), cc.OS_LEVELS[(train, guard)], cc.OS_SEED, half, negate)
+
+
+@pytest.mark.parametrize("train,guard", cc.OS_WINDOWS)
+def test_os_2d_every_rank_and_route(ctx, train, guard):
+    n, fired = cc.n_train_2d(train, guard), 0
+    for negate, scale in ((False, 1.0), (True, 2.0)):
+        planes = os_planes(train, guard, negate)
+        for k in cc.os_ranks_2d(train, guard):
+            fired += int(check_2d(ctx, planes, cc.OS, train, guard, scale, k, compact=(k == max(1, n // 2))).sum())
+    # every valid cell of the constant plane fires once the scale is one ulp below 1, and none does at 1.0
+    mask = check_2d(ctx, os_planes(train, guard, False), cc.OS, train, guard, cc.JUST_BELOW_ONE, max(1, n // 2))
+    R, D = mask.shape[1:]
+    assert mask[1].sum() == (R - 2 * (train[0] + guard[0])) * (D - 2 * (train[1] + guard[1]))
+    assert fired > 0
+
+
+@pytest.mark.parametrize("train,guard", cc.OS_SPECIALISED)
+def test_os_2d_generic_mask_kernel_for_the_specialised_windows(ctx, train, guard):
+    """MMW_OS_MASK_FORM=0 sends the two windows with a compile-time instance through the run-time-window kernel."""
+    ctx.set_option("MMW_OS_MASK_FORM", 0)
+    try:
+        for negate, scale in ((False, 1.0), (True, 2.0)):
+            for k in cc.os_ranks_2d(train, guard):
+                check_2d(ctx, os_planes(train, guard, negate), cc.OS, train, guard, scale, k, full=False)
+    finally:
+        ctx.set_option("MMW_OS_MASK_FORM", None)
+
+
+@pytest.mark.parametrize("scale", [0.0, -1.0])
+def test_os_2d_mask_only_with_a_non_positive_scale(ctx, scale):
+    train, guard = (2, 2), (1, 1)
+    for k in (1, cc.n_train_2d(train, guard) // 2, cc.n_train_2d(train, guard)):
+        mask = check_2d(ctx, os_planes(train, guard, False), cc.OS, train, guard, scale, k)
+        assert mask[0].sum() > 0
+
+
+@pytest.mark.parametrize("train,guard,shape", cc.CA_WINDOWS)
+def test_ca_2d_every_route(ctx, train, guard, shape):
+    half = (train[0] + guard[0], train[1] + guard[1])
+    n_valid = (shape[0] - 2 * half[0]) * (shape[1] - 2 * half[1])
+    for negate, scale in ((False, 1.0), (True, 2.0), (False, cc.JUST_BELOW_ONE), (True, 0.5)):
+        planes = cc.planes_2d(shape, 8, 21, half, negate)
+        mask = check_2d(ctx, planes, cc.CA, train, guard, scale, compact=(scale == 0.5))
+        assert mask[1].sum() == (n_valid if scale < 1.0 else 0)         # the constant plane sits on its threshold
+    # continuous data: the summation order shows in the last bit
+    rng = np.random.default_rng(shape[0])
+    check_2d(ctx, rng.exponential(1.0, (4,) + tuple(shape)) * 1e3, cc.CA, train, guard, 1.0)
+
+
+@pytest.mark.parametrize("kind,train,guard,k", [(cc.CA, (4, 4), (2, 2), 0), (cc.OS, (2, 2), (1, 1), 7),
+                                                (cc.CA, (1, 62), (0, 2), 0)])
+def test_degenerate_planes(ctx, kind, train, guard, k):
+    """One valid cell, one valid column, one valid row, no valid cell -- on continuous data."""
+    mask, wr, wd = cc.mask_2d(train, guard)
+    rng = np.random.default_rng(wr * wd)
+    for shape in ((wr, wd), (wr + 3, wd), (wr, wd + 3), (wr - 1, wd), (wr, wd - 1)):
+        planes = rng.exponential(1.0, (4,) + shape) * 1e3
+        planes[1] = np.round(planes[1])
+        planes[2, shape[0] // 2, shape[1] // 2] = np.inf                # an infinite cell under test
+        for scale in (1.0, 0.25):
+            ref = check_2d(ctx, planes, kind, train, guard, scale, k)
+            if shape[0] < wr or shape[1] < wd:
+                assert not ref.any()
+
+
+# ----------------------------------------------------------------------------------------------------------- 1-D
+def run_cfar1d(ctx, rows, kind, T, G, scale, k, with_thr):
+    n_rows, L = rows.shape
+    bufs = [ctx.alloc(rows.nbytes), ctx.alloc(rows.nbytes), ctx.alloc(rows.nbytes), ctx.alloc(n_rows * L)]
+    d_x, d_t, d_n, d_m = bufs
+    try:
+        d_x.upload(rows)
+        d_m.upload(np.full((n_rows, L), 7, np.uint8))
+        _lib.check(ctx.lib.mmw_cfar1d(ctx.handle, d_x.ptr, d_t.ptr if with_thr else None, d_n.ptr if with_thr else None,
+                                      d_m.ptr, n_rows, L, kind, T, G, float(scale), int(k)))
+        mask = d_m.download((n_rows, L), np.uint8)
+        if not with_thr:
+            return None, None, mask
+        return d_t.download((n_rows, L), np.float64), d_n.download((n_rows, L), np.float64), mask
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def refs_1d(rows, kind, T, G, scale, k):
+    out = [cc.ref_cfar1d(r, kind, T, G, scale, k) for r in rows]
+    return tuple(np.stack([o[i] for o in out]) for i in range(3))
+
+
+def check_1d(ctx, rows, kind, T, G, scale, k=0):
+    thr_ref, noise_ref, mask_ref = refs_1d(rows, kind, T, G, scale, k)
+    tag = f"{cc.KIND_NAMES[kind]} T {T} G {G} L {rows.shape[1]} scale {scale!r} k {k}"
+    thr, noise, mask = run_cfar1d(ctx, rows, kind, T, G, scale, k, True)
+    np.testing.assert_array_equal(noise, noise_ref, err_msg=tag + " noise")
+    np.testing.assert_array_equal(thr, thr_ref, err_msg=tag + " thresholds")
+    np.testing.assert_array_equal(mask, mask_ref, err_msg=tag + " mask")
+    mask = run_cfar1d(ctx, rows, kind, T, G, scale, k, False)[2]
+    np.testing.assert_array_equal(mask, mask_ref, err_msg=tag + " mask (mask only)")
+    return mask_ref
+
+
+@pytest.mark.parametrize("T,G", cc.WINDOWS_1D)
+@pytest.mark.parametrize("kind", [cc.CA, cc.OS, cc.GO, cc.SO])
+def test_cfar1d_rows(ctx, kind, T, G):
+    rows = cc.rows_1d(T, G)                                   # 5 x 1301: neither a multiple of 256
+    ranks = cc.os_ranks_1d(T) if kind == cc.OS else [0]
+    fired = 0
+    for scale in (1.0, 2.0, cc.JUST_BELOW_ONE):
+        for k in ranks:
+            mask = check_1d(ctx, rows, kind, T, G, scale, k)
+            fired += int(mask.sum())
+            assert mask[1].sum() == (cc.ROW_LEN - 2 * (T + G) if scale < 1.0 else 0)
+    assert fired > 0
+    # a row of exactly one window, and one cell short of it (nothing valid), on continuous, quantised and constant data
+    w = 2 * (T + G) + 1
+    rng = np.random.default_rng(T)
+    for L in (w, w - 1, w + 1):
+        short = np.stack([rng.exponential(1.0, L) * 1e3, cc.quantised(L, 6, T), cc.constant(L)])
+        for k in ranks:
+            mask = check_1d(ctx, short, kind, T, G, 0.5, k)
+            if L < w:
+                assert not mask.any()
+
+
+# ----------------------------------------------------------------------------------------------------------- gated
+@pytest.mark.parametrize("kind", [cc.CA, cc.OS, cc.GO, cc.SO])
+def test_cfar1d_gated_matches_row_by_row(ctx, kind):
+    T, G, (R, D), k = 3, 1, cc.PLANE_A, (4 if kind == cc.OS else 0)
+    planes = np.stack([cc.quantised((R, D), 6, 31), cc.nonfinite((R, D), 32, (0, T + G))[0]])
+    F = planes.shape[0]
+    mask_ref = np.stack([refs_1d(p, kind, T, G, 1.0, k)[2] for p in planes])
+    n_max = int(mask_ref.reshape(F, -1).sum(axis=1).max())
+    assert n_max > 8
+    gate = np.tile(np.array([0, R - 1], np.int32), (F, 1))
+    for cap in (R * D, n_max // 2):
+        bufs = [ctx.alloc(planes.nbytes), ctx.alloc(gate.nbytes), ctx.alloc(F * R * D), ctx.alloc(F * cap * 8), ctx.alloc(F * 4)]
+        try:
+            bufs[0].upload(planes)
+            bufs[1].upload(gate)
+            _lib.check(ctx.lib.mmw_cfar1d_gated(ctx.handle, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, bufs[4].ptr,
+                                                F, R, D, kind, T, G, 1.0, k, cap))
+            np.testing.assert_array_equal(bufs[2].download((F, R, D), np.uint8), mask_ref)
+            assert_compaction(bufs[3].download((F, cap, 2), np.int32), bufs[4].download((F,), np.int32), mask_ref, cap)
+        finally:
+            for b in bufs:
+                b.free()
+
+
+# ----------------------------------------------------------------------------------------------------------- compaction
+def test_compaction_of_fewer_cells_than_threads_and_of_a_full_mask(ctx):
+    rng = np.random.default_rng(5)
+    small = (rng.random((2, 3, 5)) < 0.5).astype(np.uint8)
+    small[1] = 1
+    dets, counts = compacted(ctx, small, 15)
+    assert_compaction(dets, counts, small, 15)
+    assert counts[1] == 15
+    ones = np.ones((2, 37, 29), np.uint8)
+    dets, counts = compacted(ctx, ones, 100)
+    assert_compaction(dets, counts, ones, 100)
+    assert counts.tolist() == [37 * 29] * 2
