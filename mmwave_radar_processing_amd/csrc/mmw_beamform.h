@@ -636,18 +636,13 @@ inline int bartlett(mmw_ctx *ctx, const void *d_X, const double *d_P, const doub
         auto kern = bf3 ? k_bartlett_tile<8, 16, false, 3> : k_bartlett_tile<8, 16, false, 1>;
         if ((E & 31) == 0) kern = poly ? k_bartlett_tile<8, 16, true, 0> : bf3 ? k_bartlett_tile<8, 16, true, 3> : k_bartlett_tile<8, 16, true, 1>;
         else if (poly) kern = k_bartlett_tile<8, 16, false, 0>;
-        long long *d_clk = nullptr;
-        if (tune_int("MMW_PHASE_CLOCKS", 0)) {
-            MMW_HIP(hipMalloc((void **)&d_clk, 5 * sizeof(long long)));
-            MMW_HIP(hipMemsetAsync(d_clk, 0, 5 * sizeof(long long), ctx->stream));
-        }
+        PhaseClocks clk;
+        if (tune_int("MMW_PHASE_CLOCKS", 0)) MMW_TRY(clk.alloc(5, ctx->stream));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, ctx->stream, (const cplx<float> *)d_X, d_P, d_dirs,
-                           (const float *)ham, Cm, S, E, T, tiles_s, NT, (int)MT, 1.0 / lambda_m, d_clk);
-        if (d_clk) {
+                           (const float *)ham, Cm, S, E, T, tiles_s, NT, (int)MT, 1.0 / lambda_m, clk.d);
+        if (clk.d) {
             long long h[5] = {0};
-            MMW_HIP(hipStreamSynchronize(ctx->stream));
-            MMW_HIP(hipMemcpy(h, d_clk, sizeof(h), hipMemcpyDeviceToHost));
-            MMW_HIP(hipFree(d_clk));
+            MMW_TRY(clk.fetch(h, 5, ctx->stream));
             std::fprintf(stderr, "bartlett tile clocks (workgroup 0 wave 0, last chunk): loads issued %lld, phase reduction %lld, "
                                  "MFMA loop %lld, reduce + store %lld\n",
                          h[1] - h[0], h[2] - h[1], h[3] - h[2], h[4] - h[3]);
@@ -1042,21 +1037,16 @@ inline int capon(mmw_ctx *ctx, const void *d_X, const double *h_thetas, float *d
                                                                                              : k_capon_sweep<4, true>)
                               : (V <= 4 ? k_capon_sweep<1, false> : V <= 8 ? k_capon_sweep<2, false> : V <= 12 ? k_capon_sweep<3, false>
                                                                                               : k_capon_sweep<4, false>);
-    if (tune_int("MMW_PHASE_CLOCKS", 0)) {
-        long long *d = nullptr, h[4] = {0};
-        MMW_HIP(hipMalloc((void **)&d, sizeof(h)));
-        MMW_HIP(hipMemsetAsync(d, 0, sizeof(h), ctx->stream));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, (const cplx<float> *)d_X,
-                           (const cplx<double> *)ctx->capon_z, d_out, V, R, K, T, n_bins, delta, d);
-        MMW_HIP(hipStreamSynchronize(ctx->stream));
-        MMW_HIP(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-        MMW_HIP(hipFree(d));
+    PhaseClocks clk;
+    if (tune_int("MMW_PHASE_CLOCKS", 0)) MMW_TRY(clk.alloc(4, ctx->stream));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, (const cplx<float> *)d_X,
+                       (const cplx<double> *)ctx->capon_z, d_out, V, R, K, T, n_bins, delta, clk.d);
+    if (clk.d) {
+        long long h[4] = {0};
+        MMW_TRY(clk.fetch(h, 4, ctx->stream));
         std::fprintf(stderr, "capon clocks (last bin of workgroup 0 wave 0): covariance %lld, sweeps %lld, spectrum %lld\n",
                      h[1] - h[0], h[2] - h[1], h[3] - h[2]);
-        return check_launch("capon");
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, (const cplx<float> *)d_X,
-                       (const cplx<double> *)ctx->capon_z, d_out, V, R, K, T, n_bins, delta, (long long *)nullptr);
     return check_launch("capon");
 }
 

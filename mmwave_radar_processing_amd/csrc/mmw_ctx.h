@@ -295,6 +295,52 @@ struct ProfScope {
     }
 };
 
+// Launches inside the scope go to queue `s` (every launcher reads ctx->stream); the previous stream is back on EVERY way out of
+// the scope.  A ProfScope opened inside it is destroyed first, so its end event still lands on `s`.
+struct StreamScope {
+    mmw_ctx *ctx;
+    hipStream_t prev;
+    StreamScope(mmw_ctx *c, hipStream_t s) : ctx(c), prev(c->stream) { c->stream = s; }
+    ~StreamScope() { ctx->stream = prev; }
+    StreamScope(const StreamScope &) = delete;
+    StreamScope &operator=(const StreamScope &) = delete;
+};
+
+// Device buffer of the MMW_PHASE_CLOCKS=1 diagnostics: n zeroed 64-bit words a kernel writes its shader clocks into (d stays
+// nullptr until alloc: "diagnostics off" for the kernels).  Freed when the scope ends, whichever way.
+struct PhaseClocks {
+    long long *d = nullptr;
+    PhaseClocks() = default;
+    PhaseClocks(const PhaseClocks &) = delete;
+    PhaseClocks &operator=(const PhaseClocks &) = delete;
+    ~PhaseClocks() {
+        if (d) (void)hipFree(d);
+    }
+    int alloc(int n, hipStream_t s) {
+        MMW_HIP(hipMalloc((void **)&d, (size_t)n * sizeof(long long)));
+        MMW_HIP(hipMemsetAsync(d, 0, (size_t)n * sizeof(long long), s));
+        return MMW_OK;
+    }
+    int fetch(long long *h, int n, hipStream_t s) {     // waits for everything enqueued on s
+        MMW_HIP(hipStreamSynchronize(s));
+        MMW_HIP(hipMemcpy(h, d, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost));
+        return MMW_OK;
+    }
+};
+
+// The CFAR windows the screening kernels know as compile-time constants -- those of the reference's own configs: (4,4)/(2,2)
+// (tests/verify_processors.py:165) and the GUI's (5,5)/(3,2) (gui_configs/processor_params.yaml:44-45) --; anything
+// else runs the <-1, -1, -1, -1> instantiation with the window as arguments.  f gets the matching tag: the ONE list of them.
+template <int TR, int TD, int GR, int GD> struct CfarWindow {
+    static constexpr int tr = TR, td = TD, gr = GR, gd = GD;
+    static constexpr bool compile_time = TR >= 0;
+};
+template <typename F> auto with_cfar_window(int tr, int td, int gr, int gd, F &&f) {
+    if (tr == 4 && td == 4 && gr == 2 && gd == 2) return f(CfarWindow<4, 4, 2, 2>{});
+    if (tr == 5 && td == 5 && gr == 3 && gd == 2) return f(CfarWindow<5, 5, 3, 2>{});
+    return f(CfarWindow<-1, -1, -1, -1>{});
+}
+
 // tuning knob read once per process from the environment (experiments only; defaults are the product path)
 inline int tune_int(const char *name, int dflt) {
     static std::map<std::string, int> cache;

@@ -1193,6 +1193,13 @@ inline bool rd_fused_supported(int S, int C) { return S == RD_S && C == RD_C; }
 int launch_rd_fused_sync(mmw_ctx *ctx, const void *d_in, void *d_ring, int n_items, ChainSync cs, int grid);   // cs.ntx > 1: raw input
 // the detection pipeline's producer: plain output cube + L1 norms, planes published per frame in cs.frame_cnt
 int launch_rd_fused_det(mmw_ctx *ctx, const void *d_in, void *d_out, float *d_l1, int n_planes, ChainSync cs, int grid);
+// ChainSync of that launch over plain cubes: words = tickets, abort word | planes published per frame
+inline ChainSync rd_ticket_sync(unsigned *words, int n_frames, int V) {
+    ChainSync cs{};
+    cs.ctl = words, cs.frame_cnt = words + CTL_CNT;
+    cs.V = cs.v_live = V, cs.n_frames = n_frames, cs.ntx = 1;
+    return cs;
+}
 // Counters of a ticketed range-Doppler launch outside the chain (tickets, abort word, one counter per frame) + a float per plane
 // for callers that do not want the L1 norms: an allocation of the context's own (mmw_detect_points runs such launches beside a
 // pending tail that owns the scratch).  Grows by reallocation behind a synchronisation of the queues that may use it.

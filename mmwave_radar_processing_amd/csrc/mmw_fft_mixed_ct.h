@@ -747,25 +747,23 @@ int launch_rd_mixed_ct_sc(mmw_ctx *ctx, const void *d_in, long in_plane_stride, 
         const unsigned resident = (unsigned)((cus > 2 * ctx->rd_leave_cus ? cus - ctx->rd_leave_cus : cus) * per_cu);
         if (grid > resident) grid = resident;
     }
+    PhaseClocks clk;
     if (tune_int("MMW_PHASE_CLOCKS", 0)) {
         // diagnostics: phase boundaries of workgroup 0 in shader clocks (marks 0..6 = start, load, range A, range B,
         // Doppler A, Doppler B, store; 8, 9 = inside the big-prime level), printed to stderr
-        long long *d = nullptr, h[10] = {0};
-        MMW_HIP(hipMalloc((void **)&d, sizeof(h)));
-        MMW_HIP(hipMemsetAsync(d, 0, sizeof(h), ctx->stream));
-        a.clk = d;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_bytes, ctx->stream, a);
-        MMW_HIP(hipStreamSynchronize(ctx->stream));
-        MMW_HIP(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-        MMW_HIP(hipFree(d));
+        MMW_TRY(clk.alloc(10, ctx->stream));
+        a.clk = clk.d;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_bytes, ctx->stream, a);
+    if (clk.d) {
+        long long h[10] = {0};
+        MMW_TRY(clk.fetch(h, 10, ctx->stream));
         std::fprintf(stderr, "rd_mixed_ct %dx%d NT=%d clocks:", S, C, NT);
         for (int i = 1; i < 7; ++i) std::fprintf(stderr, " %lld", h[i] - h[i - 1]);
         if (h[9]) std::fprintf(stderr, " | bigprime mfma %lld", h[9] - h[S1 == mixct::BIG_PRIME ? 1 : 3]);
         if (h[8]) std::fprintf(stderr, " (s / d pre-pass %lld)", h[8] - h[S1 == mixct::BIG_PRIME ? 1 : 3]);
         std::fprintf(stderr, "\n");
-        return check_launch("rd_mixed_ct");
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_bytes, ctx->stream, a);
     return check_launch("rd_mixed_ct");
 }
 

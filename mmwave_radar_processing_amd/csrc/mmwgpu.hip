@@ -27,6 +27,12 @@ int env_int(const char *name, int dflt) {
 }
 
 bool fused_rd_ok(int S, int C) { return rd_fused_supported(S, C); }
+// the fused 256 x 128 range-Doppler kernel runs (range_doppler_impl's first choice)
+bool fused_rd_runs(int S, int C) { return fused_rd_ok(S, C) && !env_int("MMW_NO_FUSED_RD", 0); }
+// the range-Doppler stage touches no scratch: the fused kernel, or a compile-time mixed-radix one (tables only)
+bool rd_needs_no_scratch(int S, int C) {
+    return fused_rd_runs(S, C) || (!fused_rd_ok(S, C) && rd_mixed_ct_supported(S, C) && !env_int("MMW_NO_MIXED_RD", 0));
+}
 
 int abs_c64(mmw_ctx *ctx, const void *d_in, float *d_out, size_t n) {
     if (n == 0) return MMW_OK;
@@ -461,7 +467,7 @@ static int range_doppler_impl(mmw_ctx *ctx, const void *d_cubes, void *d_out, vo
         // int16 raw cubes: folded into the loads of the 256 x 128 kernel and of the compile-time mixed-radix kernels (the
         // plane shapes of every shipped cfg); anything else converts + de-interleaves first (one extra pass)
         const bool i16_folded = rv.i16 && rv.ntx > 1 &&
-                                ((fused_rd_ok(S, C) && !env_int("MMW_NO_FUSED_RD", 0)) ||
+                                (fused_rd_runs(S, C) ||
                                  (rd_mixed_ct_supported(S, C) && !env_int("MMW_NO_MIXED_RD", 0)));
         if (rv.i16 && !i16_folded) {
             MMW_REQUIRE(rv.ntx >= 1 && rv.nrx >= 1, "int16 cubes are raw cubes");
@@ -474,7 +480,7 @@ static int range_doppler_impl(mmw_ctx *ctx, const void *d_cubes, void *d_out, vo
             d_cubes = d_out;
             rv = RawView{1, 0, rv.vskip, 0};
         }
-        if (fused_rd_ok(S, C) && !env_int("MMW_NO_FUSED_RD", 0))
+        if (fused_rd_runs(S, C))
             MMW_TRY(launch_rd_fused(ctx, d_cubes, d_out, n_frames * V, S, C, rv, rv.ntx > 1 ? nullptr : d_l1, &l1_done));
         else if (rd_lds_supported(S, C) && !env_int("MMW_NO_FUSED_RD", 0) && !rd_mixed_ct_supported(S, C))      // the compile-time kernel is faster where both exist (64 x 64: 6.0 vs 4.4 TB/s)
             MMW_TRY(launch_rd_lds(ctx, d_cubes, d_out, n_frames * V, S, C, rv));
@@ -1044,6 +1050,12 @@ int chain_settle(mmw_ctx *ctx) {
     MMW_HIP(hipStreamSynchronize(ctx->stream));
     return MMW_OK;
 }
+// one launch of a detection screening kernel (serial: one workgroup per frame; overlapped: persistent workgroups) on ctx->stream
+template <typename K> int launch_screen(mmw_ctx *ctx, K kern, int grid, size_t lds, const DetectArgs &a) {
+    MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(DET_NT), lds, ctx->stream, a);
+    return MMW_OK;
+}
 }  // namespace mmw
 }  // extern "C++"
 
@@ -1131,13 +1143,13 @@ static int chain3d_sync(mmw_ctx *ctx, const ChainPlan &plan, const void *d_cubes
     if (opt_int(ctx, "MMW_CHAIN_DIAG_SKIP_RD", 0)) {
         rc = MMW_OK;        // diagnostics: no producer -- the consumer's bounded spin must give up (tests of the abort path)
     } else {
-        ctx->stream = ctx->q_rd;
+        StreamScope on(ctx, ctx->q_rd);
         ProfScope ps(ctx, "rd");
         if (fused) rc = launch_rd_fused_sync(ctx, d_cubes, ctx->scratch, n_rd_items, cs, rd_grid);
         else rc = launch_rd_mixed_ct(ctx, d_cubes, (long)S * C, ctx->scratch, n_rd_items, S, C, RawView{1, 0}, &cs, plan.rd_cus, &rd_grid);
     }
     if (rc == MMW_OK) {
-        ctx->stream = ctx->q_ang;
+        StreamScope on(ctx, ctx->q_ang);
         ProfScope ps(ctx, "angle");
         switch (V) {
             case 4: rc = launch_angle64_sync<4>(ctx, ctx->scratch, d_out, bins, mag, h, shift, cs, ang_grid); break;
@@ -1146,7 +1158,6 @@ static int chain3d_sync(mmw_ctx *ctx, const ChainPlan &plan, const void *d_cubes
             default: rc = launch_angle64_sync<16>(ctx, ctx->scratch, d_out, bins, mag, h, shift, cs, ang_grid); break;
         }
     }
-    ctx->stream = main_stream;
     if (rc != MMW_OK) {
         // a launch failed: the counters no longer match the host mirror; drain and force a fresh layout next time
         (void)sync_slot_launched(ctx, false);
@@ -1243,18 +1254,21 @@ static int chain3d_impl(mmw_ctx *ctx, const void *d_cubes, RawView rv, void *d_r
         // RD(k) may overwrite its slot only after angle(k - ring) has read it
         // (also across calls: the events persist, so a back-to-back chain keeps the pipeline full)
         if (ctx->pipe_ang_used[slot]) MMW_PIPE_HIP(hipStreamWaitEvent(ctx->q_rd, ctx->pipe_ang[slot], 0));
-        ctx->stream = ctx->q_rd;
-        ctx->active_cus = rd_cus > 0 ? rd_cus : ctx->num_cu;
-        int rc = range_doppler_impl(ctx, (const char *)d_cubes + (size_t)f0 * in_frame_bytes, rd, nullptr, nf, V, S, C, rv);
-        ctx->stream = main_stream;
-        ctx->active_cus = 0;
+        int rc;
+        {
+            StreamScope on(ctx, ctx->q_rd);
+            ctx->active_cus = rd_cus > 0 ? rd_cus : ctx->num_cu;
+            rc = range_doppler_impl(ctx, (const char *)d_cubes + (size_t)f0 * in_frame_bytes, rd, nullptr, nf, V, S, C, rv);
+            ctx->active_cus = 0;
+        }
         if (rc != MMW_OK) return fail(rc);
         MMW_PIPE_HIP(hipEventRecord(ctx->pipe_rd[slot], ctx->q_rd));
         hipStream_t q_a = (n_angq == 2 && (k & 1)) ? ctx->q_ang2 : ctx->q_ang;
         MMW_PIPE_HIP(hipStreamWaitEvent(q_a, ctx->pipe_rd[slot], 0));
-        ctx->stream = q_a;
-        rc = angle_fft_impl(ctx, rd, (char *)d_out + (size_t)f0 * out_frame_bytes, nf, V, S, C, A, flags);
-        ctx->stream = main_stream;
+        {
+            StreamScope on(ctx, q_a);
+            rc = angle_fft_impl(ctx, rd, (char *)d_out + (size_t)f0 * out_frame_bytes, nf, V, S, C, A, flags);
+        }
         if (rc != MMW_OK) return fail(rc);
         MMW_PIPE_HIP(hipEventRecord(ctx->pipe_ang[slot], q_a));
         ctx->pipe_ang_used[slot] = true;
@@ -1865,7 +1879,12 @@ static int refine_parts(int n_frames) {
     return p;
 }
 
-static int fill_refine_args(mmw_ctx *ctx, RefineArgs *ra, int S, int C, int A) {
+// what every caller of launch_argmax_refine sets the same way: output buffers, antenna lists, shifts and the dense path are its own
+static int fill_refine_args(mmw_ctx *ctx, RefineArgs *ra, const void *d_cubes, const int32_t *d_dets, const int *n_flag, const int *list,
+                            int list_cap, int n_split, cplx<double> *partial, int n_frames, int V, int S, int C, int cap, int A) {
+    ra->cubes = (const float2 *)d_cubes, ra->dets = d_dets, ra->V = V, ra->cap = cap;
+    ra->n_flag = n_flag, ra->list = list, ra->list_cap = list_cap;
+    ra->partial = partial, ra->n_split = n_split, ra->parts = refine_parts(n_frames);
     const void *twA64, *twS64, *twC64, *ws64, *wc64;
     MMW_TRY(get_table<double>(ctx, TAB_TWIDDLE, A, &twA64));
     MMW_TRY(get_table<double>(ctx, TAB_TWIDDLE, S, &twS64));
@@ -1938,20 +1957,11 @@ int mmw_angle_argmax_exact(mmw_ctx *ctx, const void *d_cubes, const float *d_l1,
                         (const float2 *)twA, rf);
     MMW_TRY(check_launch("angle_argmax"));
     RefineArgs ra{};
-    MMW_TRY(fill_refine_args(ctx, &ra, S, C, A));
-    ra.cubes = (const float2 *)d_cubes;
-    ra.dets = d_dets;
-    ra.n_flag = d_nflag;
-    ra.list = d_list;
-    ra.list_cap = list_cap;
+    MMW_TRY(fill_refine_args(ctx, &ra, d_cubes, d_dets, d_nflag, d_list, list_cap, n_split, (cplx<double> *)((char *)ctx->scratch + list_bytes),
+                             n_frames, V, S, C, cap, A));
     ra.out_idx = d_idx;
-    ra.V = V;
-    ra.cap = cap;
     ra.ants = ants;
     ra.shift = shift;
-    ra.partial = (cplx<double> *)((char *)ctx->scratch + list_bytes);
-    ra.n_split = n_split;
-    ra.parts = refine_parts(n_frames);
     ra.dense_min = dense_min;
     ra.dense_cap = dense_cap;
     if (dense_min > 0) {
@@ -2037,12 +2047,11 @@ DetectPlan detect_plan(int S, int C, int kind, int tr, int td, int gr, int gd, i
     // lists of up to 8 antennas: any angle FFT size; 9 to 16: the late argmax only, i.e. 64 angle bins
     const int n_max = A == 64 ? DET_LATE_MAX_ANT : DET_MAX_ANT;
     if (kind != MMW_CFAR_CA || n_az > n_max || n_el > n_max || n > (1L << 20) || A < 1 || A > 1024) return p;
-    if (0) return p;
     p.words = (int)((n + 31) / 32);
     p.lds_cell = cell_exact_lds(S, C, 2 * hr + 1, 2 * hd + 1);
     if (p.lds_cell > 64 * 1024) return p;
-    // compile-time windows (the launch below knows the same two): four rows / columns per thread, padded band rows
-    p.ct_window = (tr == 4 && td == 4 && gr == 2 && gd == 2) || (tr == 5 && td == 5 && gr == 3 && gd == 2);
+    // compile-time windows (with_cfar_window lists them): four rows / columns per thread, padded band rows
+    p.ct_window = with_cfar_window(tr, td, gr, gd, [](auto w) { return decltype(w)::compile_time; });
     p.band_pitch = p.ct_window ? det_band_pitch(C, hd) : C;
     const int unit = p.ct_window ? 4 : 1;
     // Band of rows under test: its cells and the 2 hr halo rows travel as at most DET_LOADS loads per thread (two cells per
@@ -2066,6 +2075,418 @@ int fill_det_ant(const int *h_ant, int n_ant, int V, int A, DetAnt *out, AntList
     for (int i = 0; i < full->n && i < DET_LATE_MAX_ANT; ++i) out->idx[i] = full->idx[i];
     return MMW_OK;
 }
+
+// ---- mmw_detect_points, stage by stage (the driver is at the end)
+// Scratch of one call, as byte offsets of its regions -- each 256-byte aligned, in this order -- and their total:
+//   counters | flagged frames | undecided cells | speculative slots of the frames with undecided cells |
+//   hand-over counters (overlapped schedule only) | flagged argmax evaluations, their partial sums (with an antenna list only) |
+//   late argmax only: records, their detection slots, copy of the plane norms
+struct DetectLayout {
+    int cell_cap, list_cap, list_cap2;      // undecided cells | detection slots | flagged evaluations: both lists flag into one
+    bool late;                              // the late argmax's regions exist (their 1 GiB rule is decided here)
+    size_t ctl, flag_frames, cells, spec, sync, sync_bytes, list, part, rec_cells, rec_slot, l1_copy, total;
+};
+DetectLayout detect_layout(int n_frames, int cap, int V, int n_az, int n_el, int n_split, bool overlap, bool late_eligible) {
+    DetectLayout l{};
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    auto region = [&](size_t bytes) { const size_t off = l.total; l.total += up(bytes); return off; };     // appended behind the last
+    l.cell_cap = std::max(4096, 16 * n_frames);
+    l.list_cap = n_frames * cap;
+    l.list_cap2 = (int)std::min<long>(2L * l.list_cap, 0x7fffffffL);
+    l.ctl = region(DCTL_WORDS * sizeof(int));
+    l.flag_frames = region((size_t)n_frames * sizeof(int));
+    l.cells = region((size_t)l.cell_cap * 2 * sizeof(int));
+    l.spec = region((size_t)n_frames * (2 * DET_SPEC + 1) * sizeof(int));
+    l.sync = region(overlap ? (CTL_CNT + (size_t)n_frames) * sizeof(unsigned) : 0);      // tickets, abort word | planes published per frame
+    l.sync_bytes = l.total - l.sync;
+    if (n_az || n_el) {
+        l.list = region((size_t)std::max(l.list_cap2, 1) * sizeof(int));
+        l.part = region((size_t)std::min(l.list_cap2, n_split) * REFINE_PARTS * std::max(std::max(n_az, n_el), 1) * sizeof(cplx<double>));
+    }
+    const size_t b_rec = up((size_t)l.list_cap * (n_az + n_el) * sizeof(float2)), b_rslot = up((size_t)l.list_cap * sizeof(int32_t)),
+                 b_l1c = up((size_t)n_frames * V * sizeof(float));
+    l.late = late_eligible && b_rec + b_rslot + b_l1c <= ((size_t)1 << 30);
+    if (l.late) l.rec_cells = region(b_rec), l.rec_slot = region(b_rslot), l.l1_copy = region(b_l1c);
+    return l;
+}
+// One call: what every stage works on.  The shapes, the CFAR window and the caller's output buffers are where the kernels read
+// them: in `a` (the driver sets those fields, detect_fill_args the rest).
+struct DetectCall {
+    mmw_ctx *ctx;
+    const void *cubes;                      // the caller's input, and the outputs of the range-Doppler stage as it wants them
+    void *rd;
+    float *l1;
+    long n_train;
+    int n_az, n_el;
+    AntList az_full, el_full;
+    DetectPlan plan;
+    DetectLayout lay;
+    DetectArgs a;
+    bool overlap, refine;                   // the overlapped schedule | a float64 refinement behind the argmax (late argmax: lay.late)
+    int scr_cus, n_split;                   // CUs of the overlapped consumer | flagged evaluations whose plane sums are split
+    unsigned *sync_words;                   // scratch regions that are not part of `a`: lay.sync, lay.list, lay.part
+    int *list;
+    cplx<double> *part;
+    const void *twA, *ws64, *wc64, *twS64, *twC64;
+};
+
+int detect_check(DetectCall &d, const int *h_az, const int *h_el) {
+    const DetectArgs &a = d.a;
+    MMW_REQUIRE(a.n_frames >= 0 && a.V > 0 && a.S > 0 && a.C > 0 && a.cap >= 0 && a.A > 0, "bad shape");
+    MMW_REQUIRE(a.tr >= 0 && a.td >= 0 && a.gr >= 0 && a.gd >= 0, "negative window size");
+    MMW_REQUIRE(d.n_az >= 0 && d.n_el >= 0 && (d.n_az == 0 || a.az_idx) && (d.n_el == 0 || a.el_idx), "antenna list without an index buffer");
+    MMW_REQUIRE((long)a.n_frames * std::max(a.cap, 1) < (1L << 31) && (long)a.n_frames * 64 < (1L << 31), "too many detection slots for one call");
+    d.plan = detect_plan(a.S, a.C, a.kind, a.tr, a.td, a.gr, a.gd, d.n_az, d.n_el, a.A);
+    if (!d.plan.ok)
+        return set_error(MMW_ERR_UNSUPPORTED, "mmw_detect_points: no screening kernel for this request (CA-CFAR on planes whose "
+                         "float32 magnitudes fit the LDS, <= %d antennas per list, <= %d with 64 angle bins): use mmw_detect_batch + "
+                         "mmw_angle_argmax_exact", DET_MAX_ANT, DET_LATE_MAX_ANT);
+    const int hr = a.tr + a.gr, hd = a.td + a.gd;
+    d.n_train = (long)(2 * hr + 1) * (2 * hd + 1) - (long)(2 * a.gr + 1) * (2 * a.gd + 1);
+    MMW_REQUIRE(d.n_train >= 1 && d.n_train < (1L << 30), "empty training window");
+    if (a.kind == MMW_CFAR_OS) MMW_REQUIRE(a.k_rank >= 1 && a.k_rank <= d.n_train, "k_rank must be between 1 and %ld, got %d", d.n_train, a.k_rank);
+    MMW_TRY(fill_det_ant(h_az, d.n_az, a.V, a.A, &d.a.az, &d.az_full));
+    return fill_det_ant(h_el, d.n_el, a.V, a.A, &d.a.el, &d.el_full);
+}
+
+// tables, the schedule of this call, its scratch
+int detect_prepare(DetectCall &d) {
+    mmw_ctx *ctx = d.ctx;
+    const DetectArgs &a = d.a;
+    MMW_TRY(get_table<float>(ctx, TAB_TWIDDLE, a.A, &d.twA));
+    MMW_TRY(get_table<double>(ctx, TAB_TWIDDLE, a.S, &d.twS64));
+    MMW_TRY(get_table<double>(ctx, TAB_TWIDDLE, a.C, &d.twC64));
+    MMW_TRY(get_table<double>(ctx, TAB_HANN, a.S, &d.ws64));
+    MMW_TRY(get_table<double>(ctx, TAB_HANN, a.C, &d.wc64));
+    // Overlapped schedule (256 x 128 planes): the range-Doppler producer and the screening consumer run side by side on disjoint
+    // CU sets, frames handed over through counters in device memory.  Built, tested and MEASURED (DESIGN.md 4.9): it does not
+    // beat the serial schedule on this chip -- the range-Doppler kernel keeps its 5.2 TB/s down to ~224 CUs only, and the
+    // screening of 1250 frames needs ~70 CU-milliseconds, i.e. 2.2 ms on the 32 CUs that leaves -- so it is an option, not the
+    // default: MMW_DETECT_OVERLAP=1 selects it; MMW_DETECT_SCR_CUS = CUs of the consumer (a multiple of 32);
+    // MMW_DETECT_TAIL=0: no second consumer launch behind the producer on the producer's CUs.
+    d.scr_cus = opt_int(ctx, "MMW_DETECT_SCR_CUS", 32);
+    if (d.scr_cus < 1 || d.scr_cus >= ctx->num_cu) d.scr_cus = 32;
+    d.overlap = fused_rd_runs(a.S, a.C) && opt_int(ctx, "MMW_DETECT_OVERLAP", -1) == 1 &&
+                ensure_det_queues(ctx, ctx->num_cu - d.scr_cus) == MMW_OK;
+    // Late argmax (64 angle bins -- the reference's az_el_fft_size --, MMW_DETECT_LATE_ARGMAX=0: in the screening kernel): the
+    // screening workgroup stops at the ordered detection list and copies each detection's range-Doppler cells into a flat
+    // record list of the context; both angle estimates are launches of the lane-per-detection routine over those records
+    // (k_angle_argmax_recs: the same float32 test with the same worst-case bound) on the side queue, in front of the float64
+    // refinement -- part of the tail, so with the tail deferred they run beside the NEXT call's range-Doppler kernel, and they
+    // read nothing that call overwrites.  The in-kernel form (one wave per detection, ~1.2 detections' worth of lanes busy)
+    // cost the screening launch a third of its time: 0.27 -> 0.18 ms per 1250 frames.
+    const bool late_eligible = a.cap > 0 && d.n_az + d.n_el > 0 && a.A == 64 && opt_int(ctx, "MMW_ARGMAX_FORM", 1) == 1 &&
+                               opt_int(ctx, "MMW_DETECT_LATE_ARGMAX", 1) != 0;
+    d.n_split = std::min(a.n_frames * a.cap, std::max(0, opt_int(ctx, "MMW_REFINE_SPLIT", 32768)));
+    d.lay = detect_layout(a.n_frames, a.cap, a.V, d.n_az, d.n_el, d.n_split, d.overlap, late_eligible);
+    d.refine = a.cap > 0 && (d.n_az || d.n_el);
+    if ((d.n_az > DET_MAX_ANT || d.n_el > DET_MAX_ANT) && !d.lay.late)
+        return set_error(MMW_ERR_UNSUPPORTED, "mmw_detect_points: lists of more than %d antennas need the late argmax (64 angle bins, "
+                         "MMW_DETECT_LATE_ARGMAX / MMW_ARGMAX_FORM at their defaults, a detection capacity whose records fit 1 GiB)", DET_MAX_ANT);
+    return ensure_scratch(ctx, d.lay.total);
+}
+
+void detect_fill_args(DetectCall &d) {
+    DetectArgs &a = d.a;
+    const DetectLayout &l = d.lay;
+    char *base = (char *)d.ctx->scratch;
+    const bool lists = d.n_az || d.n_el;
+    d.sync_words = (unsigned *)(base + l.sync);
+    d.list = lists ? (int *)(base + l.list) : nullptr;
+    d.part = lists ? (cplx<double> *)(base + l.part) : nullptr;
+    a.ctl = (int *)(base + l.ctl), a.flag_frames = (int *)(base + l.flag_frames);
+    a.cells = (int *)(base + l.cells), a.cell_cap = l.cell_cap, a.spec = (int *)(base + l.spec);
+    a.words = d.plan.words, a.band_rows = d.plan.band_rows, a.band_pitch = d.plan.band_pitch, a.n_train = (int)d.n_train;
+    const float eps = 5.9604645e-8f, div = argmax_bound_div(d.ctx);
+    const int ulps = rd_error_ulps(a.S, a.C);
+    // the screening band always uses the full worst-case bound (MMW_DETECT_BAND_MULT widens it: test hook that sends more
+    // cells through the float64 decision, or -- when huge -- whole frames back to the caller)
+    a.k_fft = (float)ulps * eps * (float)std::max(1, opt_int(d.ctx, "MMW_DETECT_BAND_MULT", 1));
+    a.twA = (const float2 *)d.twA;
+    a.rf_az = ArgmaxRefine{d.l1, a.ctl + DCTL_ARGMAX, d.list, l.list_cap2, (float)ulps * eps / div, 4.f * (float)(d.n_az + 4) * eps / div};
+    a.rf_el = ArgmaxRefine{d.l1, a.ctl + DCTL_ARGMAX, d.list, l.list_cap2, (float)ulps * eps / div, 4.f * (float)(d.n_el + 4) * eps / div};
+    a.rf_el.tag = REFINE_SECOND, a.rf_el.n_tagged = a.ctl + DCTL_EL;
+    if (l.late) {
+        a.rec_cells = (float2 *)(base + l.rec_cells), a.rec_slot = (int32_t *)(base + l.rec_slot), a.rec_cap = l.list_cap;
+        a.l1_copy = (float *)(base + l.l1_copy);
+        a.rf_az.l1 = a.rf_el.l1 = a.l1_copy;
+    }
+    if (d.overlap) {
+        a.sy_ctl = d.sync_words, a.sy_frame_cnt = d.sync_words + CTL_CNT;
+        a.sy_timeout = (unsigned long long)std::max(1, opt_int(d.ctx, "MMW_CHAIN_TIMEOUT_MS", 2000)) * 100000ull;       // 100 MHz ticks
+        a.sy_naps = std::max(0, opt_int(d.ctx, "MMW_DETECT_NAPS", 4));
+    }
+}
+
+// Behind a pending tail the range-Doppler planes of a 256 x 128 batch are handed out by TICKETS (the producer kernel of the
+// overlapped schedule: it never waits for anybody; same arithmetic, sc1 stores), so that a second launch of the same kernel can
+// join in.  The counters are an allocation of their own: the scratch belongs to the pending tail.
+int detect_rd_ticketed(DetectCall &d, int grid_main, int grid_help) {
+    mmw_ctx *ctx = d.ctx;
+    const DetectArgs &a = d.a;
+    const size_t words = CTL_CNT + (size_t)a.n_frames;
+    MMW_TRY(ensure_help_sync(ctx, words));
+    const ChainSync cs = rd_ticket_sync(ctx->help_sync, a.n_frames, a.V);
+    MMW_HIP(hipMemsetAsync(ctx->help_sync, 0, words * sizeof(unsigned), ctx->stream));
+    MMW_HIP(hipEventRecord(ctx->help_begin, ctx->stream));
+    MMW_HIP(hipStreamWaitEvent(ctx->q_tail, ctx->help_begin, 0));
+    int rc;
+    {
+        ProfScope ps(ctx, "rd");
+        rc = launch_rd_fused_det(ctx, d.cubes, d.rd, d.l1, a.n_frames * a.V, cs, grid_main);
+    }
+    if (rc == MMW_OK) {
+        StreamScope on(ctx, ctx->q_tail);
+        ProfScope ps(ctx, "rd_help");
+        rc = launch_rd_fused_det(ctx, d.cubes, d.rd, d.l1, a.n_frames * a.V, cs, grid_help);
+    }
+    MMW_HIP(hipEventRecord(ctx->help_done, ctx->q_tail));       // (in any case: joined by the caller)
+    if (rc != MMW_OK) MMW_HIP(hipStreamWaitEvent(ctx->stream, ctx->help_done, 0));
+    return rc;
+}
+
+// range-Doppler of every antenna (float32) with the planes' L1 norms; joins the previous call's tail; resets the counters
+int detect_range_doppler(DetectCall &d) {
+    mmw_ctx *ctx = d.ctx;
+    const DetectArgs &a = d.a;
+    // Back-to-back calls (a frame loop over resident chunks): the previous call's tail -- exact cells, list insertion, float64
+    // refinement: ~0.15 ms of latency-bound launches that leave the chip almost idle -- is still running on its side queues.
+    // This call's range-Doppler kernel touches nothing the tail uses (the fused 256 x 128 kernel needs no scratch; its output
+    // buffers are checked against the tail's), so it goes first and the tail is joined in front of the screening stage.
+    // (the same holds for the compile-time mixed-radix kernels -- every shipped cfg's plane --: tables only, no scratch)
+    bool rd_first = !d.overlap && ctx->tail_pending && rd_needs_no_scratch(a.S, a.C), helper = false;
+    if (rd_first) {
+        const std::pair<const char *, size_t> outs[2] = {{(const char *)d.rd, (size_t)a.n_frames * a.V * a.S * a.C * 8},
+                                                         {(const char *)d.l1, (size_t)a.n_frames * a.V * sizeof(float)}};
+        for (const auto &o : outs)
+            for (const auto &t : ctx->tail_bufs)
+                if (o.first < t.first + t.second && t.first < o.first + o.second) rd_first = false;
+    }
+    if (rd_first) {
+        // the persistent kernel holds one workgroup per CU for its whole run: it leaves a few CUs to the tail's short workgroups
+        // (32 at least: with fewer some shader engine has no free CU, and the dispatcher -- which places a launch's workgroups
+        // engine by engine -- holds the tail's launches back until the range-Doppler launch ends)
+        const int leave = std::max(0, std::min(opt_int(ctx, "MMW_DETECT_TAIL_CUS", 40), ctx->num_cu / 4));
+        helper = fused_rd_runs(a.S, a.C) && a.n_frames * a.V > 4 * ctx->num_cu && leave > 0 && opt_int(ctx, "MMW_DETECT_RD_HELPER", 1) != 0;
+        if (helper) {
+            // On num_cu - leave CUs the launch is bound by CU-time (15000 planes x 23 us on 216 CUs: 1.60 ms), and the tail needs
+            // its CUs for the first ~0.7-1.0 ms only: a second launch, `leave` workgroups, sits in the tail's queue BEHIND the
+            // tail -- when the tail is done its CUs draw tickets too.
+            MMW_TRY(detect_rd_ticketed(d, ctx->num_cu - leave, leave));
+        } else {
+            ctx->rd_leave_cus = leave;
+            const int rc = range_doppler_impl(ctx, d.cubes, d.rd, nullptr, a.n_frames, a.V, a.S, a.C, RawView{1, 0}, d.l1);
+            ctx->rd_leave_cus = 0;
+            MMW_TRY(rc);
+        }
+    }
+    MMW_TRY(join_tail(ctx));
+    if (helper) MMW_HIP(hipStreamWaitEvent(ctx->stream, ctx->help_done, 0));
+    MMW_HIP(hipMemsetAsync(a.ctl, 0, DCTL_WORDS * sizeof(int), ctx->stream));      // counters
+    if (d.overlap) MMW_HIP(hipMemsetAsync(d.sync_words, 0, d.lay.sync_bytes, ctx->stream));
+    if (!d.overlap && !rd_first) MMW_TRY(range_doppler_impl(ctx, d.cubes, d.rd, nullptr, a.n_frames, a.V, a.S, a.C, RawView{1, 0}, d.l1));
+    return MMW_OK;
+}
+
+int detect_screen_serial(DetectCall &d) {
+    mmw_ctx *ctx = d.ctx;
+    ProfScope ps(ctx, "detect");
+    DetectArgs a = d.a;
+    PhaseClocks clk;       // diagnostics: shader clocks of a mid-batch workgroup's phases (load + |.|, CFAR bands, compaction, argmax)
+    if (opt_int(ctx, "MMW_PHASE_CLOCKS", 0)) MMW_TRY(clk.alloc(5, ctx->stream));
+    a.clk = clk.d;
+    MMW_TRY(with_cfar_window(a.tr, a.td, a.gr, a.gd, [&](auto w) {
+        using W = decltype(w);
+        return launch_screen(ctx, k_detect_screen<W::tr, W::td, W::gr, W::gd>, a.n_frames, d.plan.lds_screen, a);
+    }));
+    if (clk.d) {
+        long long h[5] = {0};
+        MMW_TRY(clk.fetch(h, 5, ctx->stream));
+        std::fprintf(stderr, "detect_screen %dx%d clocks: load %lld cfar %lld compact %lld argmax %lld\n", a.S, a.C, h[1] - h[0],
+                     h[2] - h[1], h[3] - h[2], h[4] - h[3]);
+    }
+    return check_launch("detect_screen");
+}
+
+// producer on q_drd, consumer on q_dscr (disjoint CU sets), both ordered behind the context stream and joined to it again
+int detect_screen_overlapped(DetectCall &d) {
+    mmw_ctx *ctx = d.ctx;
+    DetectArgs a = d.a;
+    const ChainSync cs = rd_ticket_sync(d.sync_words, a.n_frames, a.V);
+    const int n_planes = a.n_frames * a.V, rd_cus = ctx->num_cu - d.scr_cus;
+    MMW_HIP(hipEventRecord(ctx->det_begin, ctx->stream));
+    MMW_HIP(hipStreamWaitEvent(ctx->q_drd, ctx->det_begin, 0));
+    MMW_HIP(hipStreamWaitEvent(ctx->q_dscr, ctx->det_begin, 0));
+    PhaseClocks clk;       // diagnostics: phase clocks of one consumer workgroup, summed over its frames
+    if (opt_int(ctx, "MMW_PHASE_CLOCKS", 0)) MMW_TRY(clk.alloc(16, ctx->stream));
+    if (clk.d) MMW_HIP(hipStreamSynchronize(ctx->stream));
+    a.clk = clk.d;
+    auto screen = [&](int grid) -> int {
+        MMW_TRY(with_cfar_window(a.tr, a.td, a.gr, a.gd, [&](auto w) {
+            using W = decltype(w);
+            return launch_screen(ctx, k_detect_screen_sync<W::tr, W::td, W::gr, W::gd>, grid, d.plan.lds_screen, a);
+        }));
+        return check_launch("detect_screen_sync");
+    };
+    int rc = MMW_OK;
+    if (!opt_int(ctx, "MMW_DETECT_DIAG_SKIP_RD", 0)) {      // (test hook: no producer -- the consumer's bounded wait must give up)
+        StreamScope on(ctx, ctx->q_drd);
+        ProfScope ps(ctx, "rd");
+        rc = launch_rd_fused_det(ctx, d.cubes, d.rd, d.l1, n_planes, cs, std::min(rd_cus, n_planes));
+    }
+    if (rc == MMW_OK) {
+        StreamScope on(ctx, ctx->q_dscr);
+        ProfScope ps(ctx, "detect");
+        rc = screen(std::min(d.scr_cus * (1024 / DET_NT), a.n_frames));       // (512-thread workgroups: two per CU)
+    }
+    if (rc == MMW_OK && opt_int(ctx, "MMW_DETECT_TAIL", 1)) {
+        // frames the consumer's CUs have not reached when the producer drains: the same kernel (same ticket counter) on
+        // the producer's CUs, behind it in its queue
+        StreamScope on(ctx, ctx->q_drd);
+        ProfScope ps(ctx, "detect_tail");
+        rc = screen(std::min(rd_cus * (1024 / DET_NT), a.n_frames));
+    }
+    // join in any case: whatever was enqueued runs to its end (bounded waits) before the context's next work
+    MMW_HIP(hipEventRecord(ctx->det_rd_done, ctx->q_drd));
+    MMW_HIP(hipEventRecord(ctx->det_scr_done, ctx->q_dscr));
+    MMW_HIP(hipStreamWaitEvent(ctx->stream, ctx->det_rd_done, 0));
+    MMW_HIP(hipStreamWaitEvent(ctx->stream, ctx->det_scr_done, 0));
+    if (clk.d) {
+        long long h[16] = {0};
+        MMW_TRY(clk.fetch(h, 16, ctx->stream));
+        std::fprintf(stderr, "detect_screen_sync %dx%d, workgroup 0 of the consumer: %lld frames; clocks per frame: wait %lld load %lld cfar %lld "
+                     "compact %lld argmax %lld\n", a.S, a.C, h[7], h[5] / std::max(1LL, h[7]), h[0] / std::max(1LL, h[7]), h[1] / std::max(1LL, h[7]),
+                     h[2] / std::max(1LL, h[7]), h[3] / std::max(1LL, h[7]));
+        const long long nf = std::max(1LL, h[7]);
+        std::fprintf(stderr, "  band loop per frame: top %lld land(+load wait) %lld issue+barrier %lld pass1 %lld pass2 %lld pass3 %lld; candidates %lld\n",
+                     h[8] / nf, h[9] / nf, h[10] / nf, h[11] / nf, h[12] / nf, h[13] / nf, h[14] / nf);
+    }
+    return rc;
+}
+
+// the late argmax of one antenna list: one lane per record (ctx->stream)
+void launch_argmax_recs(const DetectCall &d, int off, int32_t *idx, const AntList &ants, int shift, const ArgmaxRefine &rf) {
+    if (ants.n == 0) return;
+    const DetectArgs &a = d.a;
+    const unsigned grid = (unsigned)std::max(1, std::min((d.lay.list_cap + 255) / 256, 2 * d.ctx->num_cu));
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, d.ctx->stream, (const float2 *)a.rec_cells, (const int32_t *)a.rec_slot,
+                           (const int *)(a.ctl + DCTL_RECS), a.rec_cap, d.n_az + d.n_el, off, (const float *)a.l1_copy, idx, a.V, a.cap,
+                           ants, (const float2 *)d.twA, rf);
+    };
+    if (ants.n <= 4) shift ? go(k_angle_argmax_recs<4, true>) : go(k_angle_argmax_recs<4, false>);
+    else if (ants.n <= 8) shift ? go(k_angle_argmax_recs<8, true>) : go(k_angle_argmax_recs<8, false>);
+    else shift ? go(k_angle_argmax_recs<16, true>) : go(k_angle_argmax_recs<16, false>);
+}
+// tail, side queue: angle estimates of every record (late argmax), then the float64 refinement of what the argmax flagged
+int detect_tail_refine(DetectCall &d) {
+    mmw_ctx *ctx = d.ctx;
+    const DetectArgs &a = d.a;
+    StreamScope on(ctx, ctx->q_side);
+    int rc = MMW_OK;
+    if (d.lay.late) {
+        ProfScope ps(ctx, "argmax_tail");
+        launch_argmax_recs(d, 0, a.az_idx, d.az_full, a.shift_az, a.rf_az);
+        launch_argmax_recs(d, d.n_az, a.el_idx, d.el_full, a.shift_el, a.rf_el);
+        rc = check_launch("angle_argmax_recs");
+    }
+    if (rc == MMW_OK) {
+        ProfScope ps(ctx, "argmax_refine");
+        RefineArgs ra{};
+        rc = fill_refine_args(ctx, &ra, d.cubes, a.dets, a.ctl + DCTL_ARGMAX, d.list, d.lay.list_cap2, d.n_split, d.part, a.n_frames, a.V,
+                              a.S, a.C, a.cap, a.A);
+        ra.out_idx = a.az_idx, ra.ants = d.az_full, ra.shift = a.shift_az;
+        ra.out_idx2 = a.el_idx, ra.ants2 = d.el_full, ra.shift2 = a.shift_el;
+        if (rc == MMW_OK) rc = launch_argmax_refine(ctx, ra);
+    }
+    return rc;
+}
+
+// tail, tail queue: the float64 decision of the undecided cells, then (behind the refinement) the insertion of the positive ones
+int detect_tail_exact(DetectCall &d) {
+    mmw_ctx *ctx = d.ctx;
+    const DetectArgs &a = d.a;
+    StreamScope on(ctx, ctx->q_tail);
+    ProfScope ps(ctx, "detect_exact");
+    CellExactArgs ce{};
+    ce.cubes = (const float2 *)d.cubes;
+    ce.cells = a.cells, ce.n_cells = a.ctl + DCTL_CELLS, ce.cell_cap = d.lay.cell_cap, ce.spec = a.spec;
+    ce.V = a.V, ce.S = a.S, ce.C = a.C;
+    ce.kind = a.kind, ce.tr = a.tr, ce.td = a.td, ce.gr = a.gr, ce.gd = a.gd;
+    ce.n_train = a.n_train, ce.k_rank = a.k_rank, ce.scale = a.scale;
+    ce.ws = (const double *)d.ws64, ce.wc = (const double *)d.wc64;
+    ce.twS = (const cplx<double> *)d.twS64, ce.twC = (const cplx<double> *)d.twC64;
+    PhaseClocks clk;
+    if (opt_int(ctx, "MMW_PHASE_CLOCKS", 0)) MMW_TRY(clk.alloc(5, ctx->stream));
+    ce.clk = clk.d;
+    hipLaunchKernelGGL(k_cfar_cell_exact, dim3(std::min(d.lay.cell_cap, 2 * ctx->num_cu)), dim3(CE_NT), d.plan.lds_cell, ctx->stream, ce);
+    if (clk.d) {
+        long long h[5] = {0};
+        MMW_TRY(clk.fetch(h, 5, ctx->stream));
+        std::fprintf(stderr, "cfar_cell_exact clocks: tables %lld range sums %lld doppler sums %lld decision %lld\n", h[1] - h[0], h[2] - h[1],
+                     h[3] - h[2], h[4] - h[3]);
+    }
+    int rc = check_launch("cfar_cell_exact");
+    if (d.refine) MMW_HIP(hipStreamWaitEvent(ctx->q_tail, ctx->side_join, 0));       // the refinement is done with the speculative slots
+    if (rc == MMW_OK) {
+        hipLaunchKernelGGL(k_detect_insert, dim3(std::min(a.n_frames, 4 * ctx->num_cu)), dim3(INS_NT), 0, ctx->stream, d.a);
+        rc = check_launch("detect_insert");
+    }
+    return rc;
+}
+
+// the tail is registered as pending with what it reads / writes besides the scratch; join_now: the context stream waits for it
+int detect_tail_end(DetectCall &d, bool join_now) {
+    mmw_ctx *ctx = d.ctx;
+    const DetectArgs &a = d.a;
+    MMW_HIP(hipEventRecord(ctx->tail_done, ctx->q_tail));
+    ctx->tail_pending = true;
+    const size_t slots = (size_t)a.n_frames * a.cap;
+    ctx->tail_bufs = {{(const char *)d.cubes, (size_t)a.n_frames * a.V * a.S * a.C * 8}, {(const char *)a.dets, slots * 8},
+                      {(const char *)a.counts, (size_t)a.n_frames * 4}, {(const char *)a.az_idx, a.az_idx ? slots * 4 : 0},
+                      {(const char *)a.el_idx, a.el_idx ? slots * 4 : 0}};
+    return join_now ? join_tail(ctx) : MMW_OK;
+}
+// Behind the screening: the exact decision of the undecided cells (tail queue) and the float64 refinement of the flagged
+// argmax evaluations (side queue) run SIDE BY SIDE -- neither needs the other: the frames with undecided cells carry them in
+// speculative slots --, then k_detect_insert puts the cells decided positive into their lists.
+int detect_tail(DetectCall &d, bool want_stats) {
+    mmw_ctx *ctx = d.ctx;
+    if (!ctx->q_side) {
+        MMW_HIP(hipStreamCreateWithFlags(&ctx->q_side, hipStreamNonBlocking));
+        MMW_HIP(hipStreamCreateWithFlags(&ctx->q_tail, hipStreamNonBlocking));
+        for (hipEvent_t *e : {&ctx->side_fork, &ctx->side_join, &ctx->tail_done, &ctx->help_begin, &ctx->help_done})
+            MMW_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    MMW_HIP(hipEventRecord(ctx->side_fork, ctx->stream));
+    MMW_HIP(hipStreamWaitEvent(ctx->q_tail, ctx->side_fork, 0));
+    // from here on the context stream is only the point the tail is joined to: on error, or when the caller wants the
+    // statistics / the tail is not to be deferred (MMW_DETECT_DEFER_TAIL=0), before this call returns; else at the next entry point
+    if (d.refine) {
+        MMW_HIP(hipStreamWaitEvent(ctx->q_side, ctx->side_fork, 0));
+        const int rc = detect_tail_refine(d);
+        MMW_HIP(hipEventRecord(ctx->side_join, ctx->q_side));      // (joined in any case: in front of the list insertion)
+        if (rc != MMW_OK) {
+            MMW_HIP(hipStreamWaitEvent(ctx->q_tail, ctx->side_join, 0));
+            (void)detect_tail_end(d, true);
+            return rc;
+        }
+    }
+    const int rc_tail = detect_tail_exact(d);
+    const int rc_end = detect_tail_end(d, rc_tail != MMW_OK || want_stats || !opt_int(ctx, "MMW_DETECT_DEFER_TAIL", 1));
+    MMW_TRY(rc_tail);
+    return rc_end;
+}
+
+int detect_read_stats(DetectCall &d, int *h_stats) {
+    int h[DCTL_WORDS];
+    MMW_HIP(hipMemcpyAsync(h, d.a.ctl, sizeof(h), hipMemcpyDeviceToHost, d.ctx->stream));
+    MMW_HIP(hipStreamSynchronize(d.ctx->stream));
+    h_stats[0] = h[DCTL_FLAG_FRAMES], h_stats[1] = h[DCTL_CELLS], h_stats[2] = h[DCTL_FALLBACK];
+    h_stats[3] = h[DCTL_ARGMAX] - h[DCTL_EL], h_stats[4] = h[DCTL_EL];
+    return MMW_OK;
+}
+
 }  // namespace
 
 int mmw_detect_points_supported(int S, int C, int cfar_kind, int train_r, int train_d, int guard_r, int guard_d, int n_az,
@@ -2074,459 +2495,38 @@ int mmw_detect_points_supported(int S, int C, int cfar_kind, int train_r, int tr
     return detect_plan(S, C, cfar_kind, train_r, train_d, guard_r, guard_d, n_az, n_el, A).ok ? 1 : 0;
 }
 
+// Invariants of every return path:
+//  1. ctx->stream is the context's main stream (the stages switch it with StreamScope only);
+//  2. everything enqueued on q_side, q_tail, q_drd, q_dscr is ordered before the main stream or registered as the pending tail with
+//     its buffer list (detect_tail_end).  The stages' own joins "in any case" cover a failed launch; a failed HIP call between a
+//     launch and its join is covered by ONE mechanism, the host wait for all four queues at the end of the driver, not by the guards;
+//  3. no device allocation made by the call outlives it (the diagnostics' buffers are PhaseClocks; the rest belongs to the context).
 int mmw_detect_points(mmw_ctx *ctx, const void *d_cubes, void *d_rd, float *d_l1, float *d_mag32, int32_t *d_dets,
                       int32_t *d_counts, int32_t *d_az_idx, int32_t *d_el_idx, int n_frames, int V, int S, int C, int cfar_kind,
                       int train_r, int train_d, int guard_r, int guard_d, double scale, int k_rank, int cap, const int *h_az,
                       int n_az, int shift_az, const int *h_el, int n_el, int shift_el, int A, int *h_stats) {
     MMW_REQUIRE(ctx && d_cubes && d_rd && d_l1 && d_dets && d_counts, "null argument");
-    MMW_TRY(join_pipe(ctx, true));      // (the previous call's deferred tail: joined below, behind this call's range-Doppler kernel)
-    MMW_REQUIRE(n_frames >= 0 && V > 0 && S > 0 && C > 0 && cap >= 0 && A > 0, "bad shape");
-    MMW_REQUIRE(train_r >= 0 && train_d >= 0 && guard_r >= 0 && guard_d >= 0, "negative window size");
-    MMW_REQUIRE(n_az >= 0 && n_el >= 0 && (n_az == 0 || d_az_idx) && (n_el == 0 || d_el_idx), "antenna list without an index buffer");
-    MMW_REQUIRE((long)n_frames * std::max(cap, 1) < (1L << 31) && (long)n_frames * 64 < (1L << 31), "too many detection slots for one call");
-    const DetectPlan plan = detect_plan(S, C, cfar_kind, train_r, train_d, guard_r, guard_d, n_az, n_el, A);
-    if (!plan.ok)
-        return set_error(MMW_ERR_UNSUPPORTED, "mmw_detect_points: no screening kernel for this request (CA-CFAR on planes whose "
-                         "float32 magnitudes fit the LDS, <= %d antennas per list, <= %d with 64 angle bins): use mmw_detect_batch + "
-                         "mmw_angle_argmax_exact", DET_MAX_ANT, DET_LATE_MAX_ANT);
-    const int hr = train_r + guard_r, hd = train_d + guard_d;
-    const long n_train = (long)(2 * hr + 1) * (2 * hd + 1) - (long)(2 * guard_r + 1) * (2 * guard_d + 1);
-    MMW_REQUIRE(n_train >= 1 && n_train < (1L << 30), "empty training window");
-    if (cfar_kind == MMW_CFAR_OS) MMW_REQUIRE(k_rank >= 1 && k_rank <= n_train, "k_rank must be between 1 and %ld, got %d", n_train, k_rank);
-    DetectArgs a{};
-    AntList az_full{}, el_full{};
-    MMW_TRY(fill_det_ant(h_az, n_az, V, A, &a.az, &az_full));
-    MMW_TRY(fill_det_ant(h_el, n_el, V, A, &a.el, &el_full));
-    if (h_stats)
-        for (int i = 0; i < 5; ++i) h_stats[i] = 0;
+    MMW_TRY(join_pipe(ctx, true));      // (the previous call's deferred tail: joined behind this call's range-Doppler kernel)
+    DetectCall d{};
+    DetectArgs &a = d.a;
+    d.ctx = ctx, d.cubes = d_cubes, d.rd = d_rd, d.l1 = d_l1, d.n_az = n_az, d.n_el = n_el;
+    a.rd = (const float2 *)d_rd, a.l1 = d_l1, a.mag32 = d_mag32;
+    a.dets = d_dets, a.counts = d_counts, a.az_idx = d_az_idx, a.el_idx = d_el_idx;
+    a.n_frames = n_frames, a.V = V, a.S = S, a.C = C, a.A = A, a.cap = cap, a.shift_az = shift_az, a.shift_el = shift_el;
+    a.kind = cfar_kind, a.tr = train_r, a.td = train_d, a.gr = guard_r, a.gd = guard_d, a.k_rank = k_rank, a.scale = scale;
+    MMW_TRY(detect_check(d, h_az, h_el));
+    if (h_stats) std::fill(h_stats, h_stats + 5, 0);
     if (n_frames == 0) return MMW_OK;
-    const void *twA = nullptr, *ws64, *wc64, *twS64, *twC64;
-    MMW_TRY(get_table<float>(ctx, TAB_TWIDDLE, A, &twA));
-    MMW_TRY(get_table<double>(ctx, TAB_TWIDDLE, S, &twS64));
-    MMW_TRY(get_table<double>(ctx, TAB_TWIDDLE, C, &twC64));
-    MMW_TRY(get_table<double>(ctx, TAB_HANN, S, &ws64));
-    MMW_TRY(get_table<double>(ctx, TAB_HANN, C, &wc64));
-    // scratch: counters | flagged frames | undecided cells | bit masks | flagged argmax evaluations + their partial sums
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const int cell_cap = std::max(4096, 16 * n_frames);
-    const int list_cap = n_frames * cap;
-    const int n_split = std::min(list_cap, std::max(0, opt_int(ctx, "MMW_REFINE_SPLIT", 32768)));
-    const size_t b_ctl = up(DCTL_WORDS * sizeof(int)), b_ff = up((size_t)n_frames * sizeof(int)),
-                 b_cells = up((size_t)cell_cap * 2 * sizeof(int)), b_bits = up((size_t)n_frames * (2 * DET_SPEC + 1) * sizeof(int));      // (speculative slots of the frames with undecided cells)
-    const int list_cap2 = (int)std::min<long>(2L * list_cap, 0x7fffffffL);      // both lists flag into one
-    const int n_split2 = std::min(list_cap2, n_split);
-    const size_t b_list2 = up((size_t)std::max(list_cap2, 1) * sizeof(int));
-    const size_t b_part = up((size_t)n_split2 * REFINE_PARTS * std::max(std::max(n_az, n_el), 1) * sizeof(cplx<double>));
-    // Overlapped schedule (256 x 128 planes): the range-Doppler producer and the screening consumer run side by side on disjoint
-    // CU sets, frames handed over through counters in device memory.  Built, tested and MEASURED (DESIGN.md 4.9): it does not
-    // beat the serial schedule on this chip -- the range-Doppler kernel keeps its 5.2 TB/s down to ~224 CUs only, and the
-    // screening of 1250 frames needs ~70 CU-milliseconds, i.e. 2.2 ms on the 32 CUs that leaves -- so it is an option, not the
-    // default: MMW_DETECT_OVERLAP=1 selects it; MMW_DETECT_SCR_CUS = CUs of the consumer (a multiple of 32);
-    // MMW_DETECT_TAIL=0: no second consumer launch behind the producer on the producer's CUs.
-    const int want_overlap = opt_int(ctx, "MMW_DETECT_OVERLAP", -1);
-    int scr_cus = opt_int(ctx, "MMW_DETECT_SCR_CUS", 32);
-    if (scr_cus < 1 || scr_cus >= ctx->num_cu) scr_cus = 32;
-    const bool overlap = fused_rd_ok(S, C) && !env_int("MMW_NO_FUSED_RD", 0) &&
-                         want_overlap == 1 &&
-                         ensure_det_queues(ctx, ctx->num_cu - scr_cus) == MMW_OK;
-    const size_t b_sync = overlap ? up((CTL_CNT + (size_t)n_frames) * sizeof(unsigned)) : 0;
-    size_t total = b_ctl + b_ff + b_cells + b_bits + b_sync;
-    if (n_az || n_el) total += b_list2 + b_part;
-    // Late argmax (64 angle bins -- the reference's az_el_fft_size --, MMW_DETECT_LATE_ARGMAX=0: in the screening kernel): the
-    // screening workgroup stops at the ordered detection list and copies each detection's range-Doppler cells into a flat
-    // record list of the context; both angle estimates are launches of the lane-per-detection routine over those records
-    // (k_angle_argmax_recs: the same float32 test with the same worst-case bound) on the side queue, in front of the float64
-    // refinement -- part of the tail, so with the tail deferred they run beside the NEXT call's range-Doppler kernel, and they
-    // read nothing that call overwrites.  The in-kernel form (one wave per detection, ~1.2 detections' worth of lanes busy)
-    // cost the screening launch a third of its time: 0.27 -> 0.18 ms per 1250 frames.
-    const int NV = n_az + n_el;
-    const size_t b_rec = up((size_t)list_cap * NV * sizeof(float2)), b_rslot = up((size_t)list_cap * sizeof(int32_t)),
-                 b_l1c = up((size_t)n_frames * V * sizeof(float));
-    const bool late = cap > 0 && NV > 0 && A == 64 && b_rec + b_rslot + b_l1c <= ((size_t)1 << 30) &&
-                      opt_int(ctx, "MMW_ARGMAX_FORM", 1) == 1 && opt_int(ctx, "MMW_DETECT_LATE_ARGMAX", 1) != 0;
-    if ((n_az > DET_MAX_ANT || n_el > DET_MAX_ANT) && !late)
-        return set_error(MMW_ERR_UNSUPPORTED, "mmw_detect_points: lists of more than %d antennas need the late argmax (64 angle bins, "
-                         "MMW_DETECT_LATE_ARGMAX / MMW_ARGMAX_FORM at their defaults, a detection capacity whose records fit 1 GiB)", DET_MAX_ANT);
-    const size_t off_rec = total;
-    if (late) total += b_rec + b_rslot + b_l1c;
-    MMW_TRY(ensure_scratch(ctx, total));
-    char *base = (char *)ctx->scratch;
-    a.ctl = (int *)base;
-    a.flag_frames = (int *)(base + b_ctl);
-    a.cells = (int *)(base + b_ctl + b_ff);
-    a.spec = (int *)(base + b_ctl + b_ff + b_cells);
-    unsigned *sync_words = (unsigned *)(base + b_ctl + b_ff + b_cells + b_bits);      // tickets, abort word | planes published per frame
-    char *next = base + b_ctl + b_ff + b_cells + b_bits + b_sync;
-    int *list = (n_az || n_el) ? (int *)next : nullptr;
-    cplx<double> *part = (n_az || n_el) ? (cplx<double> *)(next + b_list2) : nullptr;
-    // Back-to-back calls (a frame loop over resident chunks): the previous call's tail -- exact cells, list insertion, float64
-    // refinement: ~0.15 ms of latency-bound launches that leave the chip almost idle -- is still running on its side queues.
-    // This call's range-Doppler kernel touches nothing the tail uses (the fused 256 x 128 kernel needs no scratch; its output
-    // buffers are checked against the tail's), so it goes first and the tail is joined in front of the screening stage.
-    // (the same holds for the compile-time mixed-radix kernels -- every shipped cfg's plane --: tables only, no scratch)
-    const bool rd_no_scratch = (fused_rd_ok(S, C) && !env_int("MMW_NO_FUSED_RD", 0)) ||
-                               (!fused_rd_ok(S, C) && rd_mixed_ct_supported(S, C) && !env_int("MMW_NO_MIXED_RD", 0));
-    bool rd_first = !overlap && ctx->tail_pending && rd_no_scratch;
-    if (rd_first) {
-        const std::pair<const char *, size_t> outs[2] = {{(const char *)d_rd, (size_t)n_frames * V * S * C * 8},
-                                                         {(const char *)d_l1, (size_t)n_frames * V * sizeof(float)}};
-        for (const auto &o : outs)
-            for (const auto &t : ctx->tail_bufs)
-                if (o.first < t.first + t.second && t.first < o.first + o.second) rd_first = false;
-    }
-    // Behind a pending tail the range-Doppler planes of a 256 x 128 batch are handed out by TICKETS (the producer kernel of the
-    // overlapped schedule: it never waits for anybody; same arithmetic, sc1 stores), so that a second launch of the same kernel can
-    // join in.  The counters are an allocation of their own: the scratch belongs to the pending tail.
-    const int n_planes_all = n_frames * V;
-    const bool tickets = !overlap && fused_rd_ok(S, C) && !env_int("MMW_NO_FUSED_RD", 0) && n_planes_all > 4 * ctx->num_cu;
-    auto ticketed_rd = [&](int grid_main, int grid_help) -> int {
-        const size_t words = CTL_CNT + (size_t)n_frames;
-        MMW_TRY(ensure_help_sync(ctx, words));
-        ChainSync cs{};
-        cs.ctl = ctx->help_sync;
-        cs.frame_cnt = ctx->help_sync + CTL_CNT;
-        cs.V = cs.v_live = V;
-        cs.n_frames = n_frames;
-        cs.ntx = 1;
-        hipStream_t main_q = ctx->stream;
-        MMW_HIP(hipMemsetAsync(ctx->help_sync, 0, words * sizeof(unsigned), main_q));
-        if (grid_help > 0) {
-            MMW_HIP(hipEventRecord(ctx->help_begin, main_q));
-            MMW_HIP(hipStreamWaitEvent(ctx->q_tail, ctx->help_begin, 0));
-        }
-        int rc;
-        {
-            ProfScope ps(ctx, "rd");
-            rc = launch_rd_fused_det(ctx, d_cubes, d_rd, d_l1, n_planes_all, cs, grid_main);
-        }
-        if (grid_help > 0) {
-            if (rc == MMW_OK) {
-                ctx->stream = ctx->q_tail;
-                ProfScope ps(ctx, "rd_help");
-                rc = launch_rd_fused_det(ctx, d_cubes, d_rd, d_l1, n_planes_all, cs, grid_help);
-                ctx->stream = main_q;
-            }
-            MMW_HIP(hipEventRecord(ctx->help_done, ctx->q_tail));       // (in any case: joined by the caller)
-            if (rc != MMW_OK) MMW_HIP(hipStreamWaitEvent(main_q, ctx->help_done, 0));
-        }
-        return rc;
-    };
-    bool helper = false;
-    if (rd_first) {
-        // the persistent kernel holds one workgroup per CU for its whole run: it leaves a few CUs to the tail's short workgroups
-        // (32 at least: with fewer some shader engine has no free CU, and the dispatcher -- which places a launch's workgroups
-        // engine by engine -- holds the tail's launches back until the range-Doppler launch ends)
-        const int leave = std::max(0, std::min(opt_int(ctx, "MMW_DETECT_TAIL_CUS", 40), ctx->num_cu / 4));
-        helper = tickets && leave > 0 && opt_int(ctx, "MMW_DETECT_RD_HELPER", 1) != 0;
-        if (helper) {
-            // On num_cu - leave CUs the launch is bound by CU-time (15000 planes x 23 us on 216 CUs: 1.60 ms), and the tail needs
-            // its CUs for the first ~0.7-1.0 ms only: a second launch, `leave` workgroups, sits in the tail's queue BEHIND the
-            // tail -- when the tail is done its CUs draw tickets too.
-            MMW_TRY(ticketed_rd(ctx->num_cu - leave, leave));
-        } else {
-            ctx->rd_leave_cus = leave;
-            const int rc = range_doppler_impl(ctx, d_cubes, d_rd, nullptr, n_frames, V, S, C, RawView{1, 0}, d_l1);
-            ctx->rd_leave_cus = 0;
-            MMW_TRY(rc);
-        }
-    }
-    MMW_TRY(join_tail(ctx));
-    if (helper) MMW_HIP(hipStreamWaitEvent(ctx->stream, ctx->help_done, 0));
-    MMW_HIP(hipMemsetAsync(a.ctl, 0, DCTL_WORDS * sizeof(int), ctx->stream));      // counters
-    if (overlap) MMW_HIP(hipMemsetAsync(sync_words, 0, b_sync, ctx->stream));
-    // range-Doppler of every antenna (float32) with the planes' L1 norms
-    if (!overlap && !rd_first) MMW_TRY(range_doppler_impl(ctx, d_cubes, d_rd, nullptr, n_frames, V, S, C, RawView{1, 0}, d_l1));
-    const float eps = 5.9604645e-8f, div = argmax_bound_div(ctx);
-    const int ulps = rd_error_ulps(S, C);
-    a.rd = (const float2 *)d_rd;
-    a.l1 = d_l1;
-    a.mag32 = d_mag32;
-    a.dets = d_dets;
-    a.counts = d_counts;
-    a.az_idx = d_az_idx;
-    a.el_idx = d_el_idx;
-    a.cell_cap = cell_cap;
-    a.V = V;
-    a.S = S;
-    a.C = C;
-    a.cap = cap;
-    a.words = plan.words;
-    a.band_rows = plan.band_rows;
-    a.band_pitch = plan.band_pitch;
-    a.kind = cfar_kind;
-    a.tr = train_r;
-    a.td = train_d;
-    a.gr = guard_r;
-    a.gd = guard_d;
-    a.n_train = (int)n_train;
-    a.k_rank = k_rank;
-    a.scale = scale;
-    // the screening band always uses the full worst-case bound (MMW_DETECT_BAND_MULT widens it: test hook that sends more
-    // cells through the float64 decision, or -- when huge -- whole frames back to the caller)
-    a.k_fft = (float)ulps * eps * (float)std::max(1, opt_int(ctx, "MMW_DETECT_BAND_MULT", 1));
-    a.A = A;
-    a.shift_az = shift_az;
-    a.shift_el = shift_el;
-    a.twA = (const float2 *)twA;
-    a.rf_az = ArgmaxRefine{d_l1, a.ctl + DCTL_ARGMAX, list, list_cap2, (float)ulps * eps / div, 4.f * (float)(n_az + 4) * eps / div};
-    a.rf_el = ArgmaxRefine{d_l1, a.ctl + DCTL_ARGMAX, list, list_cap2, (float)ulps * eps / div, 4.f * (float)(n_el + 4) * eps / div};
-    a.rf_el.tag = REFINE_SECOND;
-    a.rf_el.n_tagged = a.ctl + DCTL_EL;
-    a.n_frames = n_frames;
-    if (late) {
-        a.rec_cells = (float2 *)(base + off_rec);
-        a.rec_slot = (int32_t *)(base + off_rec + b_rec);
-        a.l1_copy = (float *)(base + off_rec + b_rec + b_rslot);
-        a.rec_cap = list_cap;
-        a.rf_az.l1 = a.rf_el.l1 = a.l1_copy;
-    }
-    if (overlap) {
-        a.sy_ctl = sync_words;
-        a.sy_frame_cnt = sync_words + CTL_CNT;
-        a.sy_timeout = (unsigned long long)std::max(1, opt_int(ctx, "MMW_CHAIN_TIMEOUT_MS", 2000)) * 100000ull;       // 100 MHz ticks
-        a.sy_naps = std::max(0, opt_int(ctx, "MMW_DETECT_NAPS", 4));
-        ChainSync cs{};
-        cs.ctl = sync_words;
-        cs.frame_cnt = a.sy_frame_cnt;
-        cs.V = cs.v_live = V;
-        cs.n_frames = n_frames;
-        cs.ntx = 1;
-        const int n_planes = n_frames * V, rd_cus = ctx->num_cu - scr_cus;
-        hipStream_t main_stream = ctx->stream;
-        MMW_HIP(hipEventRecord(ctx->det_begin, main_stream));
-        MMW_HIP(hipStreamWaitEvent(ctx->q_drd, ctx->det_begin, 0));
-        MMW_HIP(hipStreamWaitEvent(ctx->q_dscr, ctx->det_begin, 0));
-        auto screen = [&](int grid) -> int {
-            auto go = [&](auto kern) -> int {
-                MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_screen));
-                hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(DET_NT), plan.lds_screen, ctx->stream, a);
-                return check_launch("detect_screen_sync");
-            };
-            if (train_r == 4 && train_d == 4 && guard_r == 2 && guard_d == 2) return go(k_detect_screen_sync<4, 4, 2, 2>);
-            if (train_r == 5 && train_d == 5 && guard_r == 3 && guard_d == 2) return go(k_detect_screen_sync<5, 5, 3, 2>);
-            return go(k_detect_screen_sync<-1, -1, -1, -1>);
-        };
-        long long *d_clk = nullptr;
-        if (opt_int(ctx, "MMW_PHASE_CLOCKS", 0)) {              // diagnostics: phase clocks of one consumer workgroup, summed over its frames
-            MMW_HIP(hipMalloc((void **)&d_clk, 16 * sizeof(long long)));
-            MMW_HIP(hipMemsetAsync(d_clk, 0, 16 * sizeof(long long), main_stream));
-            MMW_HIP(hipStreamSynchronize(main_stream));
-            a.clk = d_clk;
-        }
-        int rc = MMW_OK;
-        if (!opt_int(ctx, "MMW_DETECT_DIAG_SKIP_RD", 0)) {      // (test hook: no producer -- the consumer's bounded wait must give up)
-            ctx->stream = ctx->q_drd;
-            ProfScope ps(ctx, "rd");
-            rc = launch_rd_fused_det(ctx, d_cubes, d_rd, d_l1, n_planes, cs, std::min(rd_cus, n_planes));
-        }
-        if (rc == MMW_OK) {
-            ctx->stream = ctx->q_dscr;
-            ProfScope ps(ctx, "detect");
-            rc = screen(std::min(scr_cus * (1024 / DET_NT), n_frames));       // (512-thread workgroups: two per CU)
-        }
-        if (rc == MMW_OK && opt_int(ctx, "MMW_DETECT_TAIL", 1)) {
-            // frames the consumer's CUs have not reached when the producer drains: the same kernel (same ticket counter) on
-            // the producer's CUs, behind it in its queue
-            ctx->stream = ctx->q_drd;
-            ProfScope ps(ctx, "detect_tail");
-            rc = screen(std::min(rd_cus * (1024 / DET_NT), n_frames));
-        }
-        ctx->stream = main_stream;
-        // join in any case: whatever was enqueued runs to its end (bounded waits) before the context's next work
-        MMW_HIP(hipEventRecord(ctx->det_rd_done, ctx->q_drd));
-        MMW_HIP(hipEventRecord(ctx->det_scr_done, ctx->q_dscr));
-        MMW_HIP(hipStreamWaitEvent(main_stream, ctx->det_rd_done, 0));
-        MMW_HIP(hipStreamWaitEvent(main_stream, ctx->det_scr_done, 0));
-        if (d_clk) {
-            long long h[16] = {0};
-            MMW_HIP(hipStreamSynchronize(main_stream));
-            MMW_HIP(hipMemcpy(h, d_clk, sizeof(h), hipMemcpyDeviceToHost));
-            MMW_HIP(hipFree(d_clk));
-            a.clk = nullptr;
-            std::fprintf(stderr, "detect_screen_sync %dx%d, workgroup 0 of the consumer: %lld frames; clocks per frame: wait %lld load %lld cfar %lld "
-                         "compact %lld argmax %lld\n", S, C, h[7], h[5] / std::max(1LL, h[7]), h[0] / std::max(1LL, h[7]), h[1] / std::max(1LL, h[7]),
-                         h[2] / std::max(1LL, h[7]), h[3] / std::max(1LL, h[7]));
-            const long long nf = std::max(1LL, h[7]);
-            std::fprintf(stderr, "  band loop per frame: top %lld land(+load wait) %lld issue+barrier %lld pass1 %lld pass2 %lld pass3 %lld; candidates %lld\n",
-                         h[8] / nf, h[9] / nf, h[10] / nf, h[11] / nf, h[12] / nf, h[13] / nf, h[14] / nf);
-        }
-        MMW_TRY(rc);
-    } else {
-        ProfScope ps(ctx, "detect");
-        auto go = [&](auto kern) -> int {
-            MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_screen));
-            if (tune_int("MMW_PHASE_CLOCKS", 0)) {
-                // diagnostics: shader clocks of a mid-batch workgroup's phases (load + |.|, CFAR bands, compaction, argmax)
-                long long *d = nullptr, h[5] = {0};
-                MMW_HIP(hipMalloc((void **)&d, sizeof(h)));
-                MMW_HIP(hipMemsetAsync(d, 0, sizeof(h), ctx->stream));
-                DetectArgs b = a;
-                b.clk = d;
-                hipLaunchKernelGGL(kern, dim3((unsigned)n_frames), dim3(DET_NT), plan.lds_screen, ctx->stream, b);
-                MMW_HIP(hipStreamSynchronize(ctx->stream));
-                MMW_HIP(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-                MMW_HIP(hipFree(d));
-                std::fprintf(stderr, "detect_screen %dx%d clocks: load %lld cfar %lld compact %lld argmax %lld\n", S, C, h[1] - h[0],
-                             h[2] - h[1], h[3] - h[2], h[4] - h[3]);
-                return MMW_OK;
-            }
-            hipLaunchKernelGGL(kern, dim3((unsigned)n_frames), dim3(DET_NT), plan.lds_screen, ctx->stream, a);
-            return MMW_OK;
-        };
-        // the windows of the reference's own configs as compile-time constants: (4,4)/(2,2) (tests/verify_processors.py:165,
-        // SURVEY.md 8d) and the GUI's (5,5)/(3,2) (gui_configs/processor_params.yaml:44-45); anything else at run time
-        if (train_r == 4 && train_d == 4 && guard_r == 2 && guard_d == 2) MMW_TRY(go(k_detect_screen<4, 4, 2, 2>));
-        else if (train_r == 5 && train_d == 5 && guard_r == 3 && guard_d == 2) MMW_TRY(go(k_detect_screen<5, 5, 3, 2>));
-        else MMW_TRY(go(k_detect_screen<-1, -1, -1, -1>));
-        MMW_TRY(check_launch("detect_screen"));
-    }
-    // Behind the screening: the exact decision of the undecided cells (context stream) and the float64 refinement of the flagged
-    // argmax evaluations (side stream) run SIDE BY SIDE -- neither needs the other: the frames with undecided cells carry them in
-    // speculative slots --, then k_detect_insert puts the cells decided positive into their lists.
-    const bool refine = cap > 0 && (n_az || n_el);
-    hipStream_t main_stream = ctx->stream;
-    if (!ctx->q_side) {
-        MMW_HIP(hipStreamCreateWithFlags(&ctx->q_side, hipStreamNonBlocking));
-        MMW_HIP(hipStreamCreateWithFlags(&ctx->q_tail, hipStreamNonBlocking));
-        MMW_HIP(hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming));
-        MMW_HIP(hipEventCreateWithFlags(&ctx->side_join, hipEventDisableTiming));
-        MMW_HIP(hipEventCreateWithFlags(&ctx->tail_done, hipEventDisableTiming));
-        MMW_HIP(hipEventCreateWithFlags(&ctx->help_begin, hipEventDisableTiming));
-        MMW_HIP(hipEventCreateWithFlags(&ctx->help_done, hipEventDisableTiming));
-    }
-    MMW_HIP(hipEventRecord(ctx->side_fork, main_stream));
-    MMW_HIP(hipStreamWaitEvent(ctx->q_tail, ctx->side_fork, 0));
-    // from here on the context stream is only the point the tail is joined to: on error, or when the caller wants the
-    // statistics / the tail is not to be deferred (MMW_DETECT_DEFER_TAIL=0), before this call returns; else at the next entry point
-    auto tail_end = [&](bool join_now) -> int {
-        MMW_HIP(hipEventRecord(ctx->tail_done, ctx->q_tail));
-        ctx->tail_pending = true;
-        ctx->tail_bufs = {{(const char *)d_cubes, (size_t)n_frames * V * S * C * 8}, {(const char *)d_dets, (size_t)n_frames * cap * 8},
-                          {(const char *)d_counts, (size_t)n_frames * 4}, {(const char *)d_az_idx, d_az_idx ? (size_t)n_frames * cap * 4 : 0},
-                          {(const char *)d_el_idx, d_el_idx ? (size_t)n_frames * cap * 4 : 0}};
-        return join_now ? join_tail(ctx) : MMW_OK;
-    };
-    if (refine) {
-        MMW_HIP(hipStreamWaitEvent(ctx->q_side, ctx->side_fork, 0));
-        ctx->stream = ctx->q_side;
-        int rc = MMW_OK;
-        if (late) {
-            // angle estimates of every record (one lane each), then the float64 refinement of what they flag
-            ProfScope ps(ctx, "argmax_tail");
-            const unsigned grid = (unsigned)std::max(1, std::min((list_cap + 255) / 256, 2 * ctx->num_cu));
-            auto recs = [&](auto kern, int off, int32_t *idx, const AntList &ants, const ArgmaxRefine &rf) {
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, ctx->stream, (const float2 *)a.rec_cells, (const int32_t *)a.rec_slot,
-                                   (const int *)(a.ctl + DCTL_RECS), a.rec_cap, NV, off, (const float *)a.l1_copy, idx, V, cap, ants,
-                                   (const float2 *)twA, rf);
-            };
-            auto one_list = [&](int off, int32_t *idx, const AntList &ants, int shift, const ArgmaxRefine &rf) {
-                if (ants.n == 0) return;
-                if (ants.n <= 4) {
-                    if (shift) recs(k_angle_argmax_recs<4, true>, off, idx, ants, rf); else recs(k_angle_argmax_recs<4, false>, off, idx, ants, rf);
-                } else if (ants.n <= 8) {
-                    if (shift) recs(k_angle_argmax_recs<8, true>, off, idx, ants, rf); else recs(k_angle_argmax_recs<8, false>, off, idx, ants, rf);
-                } else {
-                    if (shift) recs(k_angle_argmax_recs<16, true>, off, idx, ants, rf); else recs(k_angle_argmax_recs<16, false>, off, idx, ants, rf);
-                }
-            };
-            one_list(0, d_az_idx, az_full, shift_az, a.rf_az);
-            one_list(n_az, d_el_idx, el_full, shift_el, a.rf_el);
-            rc = check_launch("angle_argmax_recs");
-        }
-        if (rc == MMW_OK) {
-            ProfScope ps(ctx, "argmax_refine");
-            RefineArgs ra{};
-            rc = fill_refine_args(ctx, &ra, S, C, A);
-            ra.cubes = (const float2 *)d_cubes;
-            ra.dets = d_dets;
-            ra.n_flag = a.ctl + DCTL_ARGMAX;
-            ra.list = list;
-            ra.list_cap = list_cap2;
-            ra.out_idx = d_az_idx;
-            ra.out_idx2 = d_el_idx;
-            ra.V = V;
-            ra.cap = cap;
-            ra.ants = az_full;
-            ra.ants2 = el_full;
-            ra.shift = shift_az;
-            ra.shift2 = shift_el;
-            ra.partial = part;
-            ra.n_split = n_split2;
-            ra.parts = refine_parts(n_frames);
-            if (rc == MMW_OK) rc = launch_argmax_refine(ctx, ra);
-        }
-        ctx->stream = main_stream;
-        MMW_HIP(hipEventRecord(ctx->side_join, ctx->q_side));      // (joined below in any case: in front of the list insertion)
-        if (rc != MMW_OK) {
-            MMW_HIP(hipStreamWaitEvent(ctx->q_tail, ctx->side_join, 0));
-            (void)tail_end(true);
-            return rc;
-        }
-    }
-    ctx->stream = ctx->q_tail;
-    int rc_tail = MMW_OK;
-    {
-        ProfScope ps(ctx, "detect_exact");
-        CellExactArgs ce{};
-        ce.cubes = (const float2 *)d_cubes;
-        ce.cells = a.cells;
-        ce.n_cells = a.ctl + DCTL_CELLS;
-        ce.cell_cap = cell_cap;
-        ce.spec = a.spec;
-        ce.V = V;
-        ce.S = S;
-        ce.C = C;
-        ce.kind = cfar_kind;
-        ce.tr = train_r;
-        ce.td = train_d;
-        ce.gr = guard_r;
-        ce.gd = guard_d;
-        ce.n_train = (int)n_train;
-        ce.k_rank = k_rank;
-        ce.scale = scale;
-        ce.ws = (const double *)ws64;
-        ce.wc = (const double *)wc64;
-        ce.twS = (const cplx<double> *)twS64;
-        ce.twC = (const cplx<double> *)twC64;
-        long long *d_clk = nullptr;
-        if (tune_int("MMW_PHASE_CLOCKS", 0)) {
-            MMW_HIP(hipMalloc((void **)&d_clk, 5 * sizeof(long long)));
-            MMW_HIP(hipMemsetAsync(d_clk, 0, 5 * sizeof(long long), ctx->stream));
-            ce.clk = d_clk;
-        }
-        hipLaunchKernelGGL(k_cfar_cell_exact, dim3(std::min(cell_cap, 2 * ctx->num_cu)), dim3(CE_NT), plan.lds_cell, ctx->stream, ce);
-        if (d_clk) {
-            long long h[5] = {0};
-            MMW_HIP(hipStreamSynchronize(ctx->stream));
-            MMW_HIP(hipMemcpy(h, d_clk, sizeof(h), hipMemcpyDeviceToHost));
-            MMW_HIP(hipFree(d_clk));
-            std::fprintf(stderr, "cfar_cell_exact clocks: tables %lld range sums %lld doppler sums %lld decision %lld\n", h[1] - h[0], h[2] - h[1],
-                         h[3] - h[2], h[4] - h[3]);
-        }
-        rc_tail = check_launch("cfar_cell_exact");
-        if (refine) MMW_HIP(hipStreamWaitEvent(ctx->q_tail, ctx->side_join, 0));       // the refinement is done with the speculative slots
-        if (rc_tail == MMW_OK) {
-            hipLaunchKernelGGL(k_detect_insert, dim3(std::min(n_frames, 4 * ctx->num_cu)), dim3(INS_NT), 0, ctx->stream, a);
-            rc_tail = check_launch("detect_insert");
-        }
-    }
-    ctx->stream = main_stream;
-    {
-        const int rc_end = tail_end(rc_tail != MMW_OK || h_stats != nullptr || !opt_int(ctx, "MMW_DETECT_DEFER_TAIL", 1));
-        MMW_TRY(rc_tail);
-        MMW_TRY(rc_end);
-    }
-    if (h_stats) {
-        int h[DCTL_WORDS];
-        MMW_HIP(hipMemcpyAsync(h, a.ctl, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        MMW_HIP(hipStreamSynchronize(ctx->stream));
-        h_stats[0] = h[DCTL_FLAG_FRAMES];
-        h_stats[1] = h[DCTL_CELLS];
-        h_stats[2] = h[DCTL_FALLBACK];
-        h_stats[3] = h[DCTL_ARGMAX] - h[DCTL_EL];
-        h_stats[4] = h[DCTL_EL];
-    }
-    return MMW_OK;
+    MMW_TRY(detect_prepare(d));
+    detect_fill_args(d);
+    int rc = detect_range_doppler(d);
+    if (rc == MMW_OK) rc = d.overlap ? detect_screen_overlapped(d) : detect_screen_serial(d);
+    if (rc == MMW_OK) rc = detect_tail(d, h_stats != nullptr);
+    if (rc == MMW_OK && h_stats) rc = detect_read_stats(d, h_stats);
+    if (rc != MMW_OK)       // invariant 2 on every failure path (also waits for a previous call's pending tail: errors only)
+        for (hipStream_t q : {ctx->q_drd, ctx->q_dscr, ctx->q_side, ctx->q_tail})
+            if (q) (void)hipStreamSynchronize(q);
+    return rc;
 }
 
 int mmw_angle_argmax_cells64(mmw_ctx *ctx, const void *d_cells, int32_t *d_idx, int n_rows, int n_ant, int A, int shift) {
