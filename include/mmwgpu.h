@@ -277,6 +277,31 @@ int mmw_seq_detect_plane(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_row
                          int num_train, int num_guard, double scale, int k_rank, int cap);
 int mmw_seq_route(mmw_ctx *ctx, int S, int C);
 
+/* Device point clouds and batched ego velocity (FramePipeline.point_clouds_device / ego_velocities).
+ * mmw_point_cloud: d_points[F][cap][4] float64 (x, y, z, v) of the detections d_dets[F][cap][2] / d_counts[F] and their angle
+ *   bins d_az_idx / d_el_idx [F][cap] (either may be NULL: angle 0), as point_cloud_generator.py:216-248 forms them:
+ *   x = (rng * cos_el) * cos_az, y = (rng * cos_el) * sin_az, z = rng * sin_el, every product one round-to-nearest multiply
+ *   of entries of the caller's float64 tables d_range_bins[S], d_vel_bins[C], d_cos[A], d_sin[A] (np.cos / np.sin of the
+ *   angle bins, made on the host).  Slots past a frame's count (counts are clamped to cap) are zeroed.
+ * mmw_ego_velocity_ransac: per frame, with N = d_counts[f] points, y = -v and H = p[:dim] / |p[:dim]| (dim 2 or 3), what
+ *   RANSACRegressor(LinearRegression(fit_intercept=False), min_samples=10, residual_threshold=thr, max_trials=20,
+ *   random_state=42).fit(H, y) of scikit-learn 1.7.2 decides, the refit on the best inlier set, its R^2 on them (0 for at most
+ *   3 inliers) and the inlier share: d_out[F][dim + 2].  Zeros when N < 10 or no trial is accepted (the fit's ValueError).
+ *   Trial t of a frame fits the points d_subsets[d_subset_row[f]][t][0..9] (the caller's draws of sample_without_replacement for
+ *   this N); accepting a trial with k inliers caps the trial count at d_trials_tab[d_trials_off[row] + k] (the caller's
+ *   min(20, _dynamic_max_trials(k, N, 10, 0.99)), k = 0 .. N).  n_rows / tab_len: extents of the tables, checked per frame.
+ *   d_flags[F]: 0, or the reasons (1 residual at thr, 2 tied scores, 4 R^2 at r2_thr or ill-defined, 8 condition beyond 1e6,
+ *   16 non-finite point, 32 table row does not serve N) why the frame's decisions are within rounding of scikit-learn's
+ *   SVD solve: its d_out row is zero and the caller recomputes it.  d_inlier_mask: NULL, or [F][cap] uint8.
+ *   4 * cap + 48 doubles of LDS: MMW_ERR_UNSUPPORTED beyond 160 KiB. */
+int mmw_point_cloud(mmw_ctx *ctx, const int32_t *d_dets, const int32_t *d_counts, const int32_t *d_az_idx, const int32_t *d_el_idx,
+                    const double *d_range_bins, const double *d_vel_bins, const double *d_cos, const double *d_sin,
+                    double *d_points, int n_frames, int cap, int S, int C, int A);
+int mmw_ego_velocity_ransac(mmw_ctx *ctx, const double *d_points, const int32_t *d_counts, int n_frames, int cap, int dim,
+                            double thr, double r2_thr, const int32_t *d_subsets, const int32_t *d_subset_row, int n_rows,
+                            const int32_t *d_trials_tab, int tab_len, const int32_t *d_trials_off, double *d_out,
+                            int32_t *d_flags, uint8_t *d_inlier_mask);
+
 /* mmw_detect_batch: the detection pipeline of RangeDopplerDetector2D for a batch of frames in one call:
  *   d_rd[F][V][S][C] c64 (mmw_range_doppler) and, for antenna 0, d_mag64[F][S][C] -> 2-D CFAR mask -> ordered
  *   detections d_dets[F][cap][2] / d_counts[F]

@@ -35,3 +35,13 @@ class LazyAttrs:
         if lazy:
             lazy.pop(name, None)
         object.__setattr__(self, name, value)
+
+
+def lazy_import(name: str):
+    """Import an optional dependency where it is first needed (scikit-learn for the ego-velocity estimator): the package
+    itself imports without it, and the error of a host that lacks it names what asked for it."""
+    import importlib
+    try:
+        return importlib.import_module(name)
+    except ImportError as e:
+        raise ImportError(f"{name} is needed here (and only here) and cannot be imported: {e}") from e

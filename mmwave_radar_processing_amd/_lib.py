@@ -91,6 +91,8 @@ _SIGNATURES = {
     "mmw_seq_detect": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _vp],
     "mmw_seq_detect_plane": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i],
     "mmw_seq_route": [_vp, _i, _i],
+    "mmw_point_cloud": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i],
+    "mmw_ego_velocity_ransac": [_vp, _vp, _vp, _i, _i, _i, _d, _d, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp],
     "mmw_detect_points_supported": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i],
     "mmw_detect_points": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i,
                           _ip, _i, _i, _ip, _i, _i, _i, _ip],

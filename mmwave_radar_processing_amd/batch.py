@@ -389,12 +389,15 @@ class FramePipeline:
             counts = self.d_cnt.download((F,), np.int32)
         return counts
 
+    def _check_capacity(self, counts) -> None:
+        self.counts = counts
+        if np.any(counts > self.cap):
+            raise _lib.MmwGpuError(f"detection capacity {self.cap} exceeded (max count {int(counts.max())}): "
+                                   "raise det_capacity")
+
     def _fetch_dets(self, counts) -> List[np.ndarray]:
         F, cap = self.n_frames, self.cap
-        self.counts = counts
-        if np.any(counts > cap):
-            raise _lib.MmwGpuError(f"detection capacity {cap} exceeded (max count {int(counts.max())}): "
-                                   "raise det_capacity")
+        self._check_capacity(counts)
         dets = self.d_dets.download((F, cap, 2), np.int32)
         self.dets = [dets[f, :counts[f]].astype(np.int64) for f in range(F)]
         return self.dets
@@ -517,39 +520,52 @@ class FramePipeline:
         ``ground=``: the ground detector's detections (gated rows, Doppler CFAR), and ``altitudes`` is set.  With
         ``sequential=``: the sequential detector's detections; the float32 RD cube is not computed (``point_clouds()``
         computes it for the argmax)."""
-        F = self.n_frames
         self._alloc_detect()
+        return self._fetch_dets(self._detect_counts())
+
+    def _detect_counts(self) -> np.ndarray:
+        """The detections of ``detect()`` left on the device (``d_dets`` / ``d_cnt``); returns the counts."""
+        F = self.n_frames
         if self.ground is not None:
-            return self._fetch_dets(self._detect_ground())
+            return self._detect_ground()
         if self.sequential is not None:
-            return self._fetch_dets(self._detect_sequential(False))
+            return self._detect_sequential(False)
         if self._fused_supported(False):
-            return self._fetch_dets(self._detect_fused(False))
+            return self._detect_fused(False)
         for f0 in range(0, F, 32768):       # grid limits of the per-frame launches
             self._detect_float64(f0, min(32768, F - f0))
-        return self._fetch_dets(self.d_cnt.download((F,), np.int32))
+        return self.d_cnt.download((F,), np.int32)
 
-    def _argmax(self, ant, shift, name) -> np.ndarray:
-        """Exact (float64-equivalent) argmax bins of every detection: ``mmw_angle_argmax_exact``."""
+    def _argmax_device(self, ant, shift, name) -> _lib.DeviceBuffer:
+        """Exact (float64-equivalent) argmax bins of every detection, ``[F, cap]`` int32 on the device: ``mmw_angle_argmax_exact``."""
         F, cap = self.n_frames, self.cap
         d_idx = self.bufs.get(name, max(F, 1) * cap * 4)
         for f0 in range(0, F, 32768):
             self._argmax_float64(d_idx, ant, shift, f0, min(32768, F - f0))
-        return d_idx.download((F, cap), np.int32)
+        return d_idx
+
+    def _detect_points(self, fetch: bool) -> np.ndarray:
+        """Detections and their angle bins for every frame, left on the device (``d_dets``, ``d_cnt``, ``d_az``, ``d_el``; an
+        empty antenna list leaves None).  ``fetch``: also the host lists of ``detect()`` (``self.dets``).  Returns the counts."""
+        self.n_refined = 0      # detections re-evaluated in float64 (near-ties of the float32 pass)
+        self._alloc_detect()
+        if self.ground is None and self.sequential is None and self._fused_supported(True):
+            counts = self._detect_fused(True)
+            self._fetch_dets(counts) if fetch else self._check_capacity(counts)
+            return counts
+        counts = self._detect_sequential(True) if self.sequential is not None else self._detect_counts()
+        self._fetch_dets(counts) if fetch else self._check_capacity(counts)
+        self.d_az = self._argmax_device(self.az, self.shift_az, "az_idx") if self.az else None
+        self.d_el = self._argmax_device(self.el, self.shift_el, "el_idx") if self.el else None
+        return counts
 
     def point_clouds(self) -> List[np.ndarray]:
         """Per-frame float64 ``(N, 4)`` (x, y, z, velocity), FLU frame (point_cloud_generator.py:216-248)."""
-        self.n_refined = 0      # detections re-evaluated in float64 (near-ties of the float32 pass)
         F, cap = self.n_frames, self.cap
-        self._alloc_detect()
-        if self.ground is None and self.sequential is None and self._fused_supported(True):
-            dets = self._fetch_dets(self._detect_fused(True))
-            az_idx = self.d_az.download((F, cap), np.int32) if self.az else None
-            el_idx = self.d_el.download((F, cap), np.int32) if self.el else None
-        else:
-            dets = self._fetch_dets(self._detect_sequential(True)) if self.sequential is not None else self.detect()
-            az_idx = self._argmax(self.az, self.shift_az, "az_idx") if self.az else None
-            el_idx = self._argmax(self.el, self.shift_el, "el_idx") if self.el else None
+        self._detect_points(True)
+        dets = self.dets
+        az_idx = self.d_az.download((F, cap), np.int32) if self.az else None
+        el_idx = self.d_el.download((F, cap), np.int32) if self.el else None
         out = []
         for f, d in enumerate(dets):
             n = d.shape[0]
@@ -564,6 +580,130 @@ class FramePipeline:
         self.az_idx = None if az_idx is None else [az_idx[f, :len(d)].astype(np.int64) for f, d in enumerate(dets)]
         self.el_idx = None if el_idx is None else [el_idx[f, :len(d)].astype(np.int64) for f, d in enumerate(dets)]
         return out
+
+    # ------------------------------------------------------------------ device point clouds, ego velocity
+    def point_clouds_device(self) -> _lib.DeviceBuffer:
+        """``point_clouds()`` without the download and the per-frame host loop: a packed float64 ``[F, cap, 4]`` (x, y, z,
+        velocity) buffer in HBM (``mmw_point_cloud``), frame f holding its ``counts[f]`` points first and zeros behind them.
+        ``fetch_point_clouds()`` downloads it to the lists ``point_clouds()`` returns, bit for bit."""
+        F, cap = self.n_frames, self.cap
+        self._detect_points(False)
+        tabs = self.__dict__.get("_pc_tables")
+        if tabs is None:                    # float64 tables made on the host (no device libm), uploaded once
+            tabs = tuple(self.bufs.get(f"pc_tab{i}", t.nbytes) for i, t in enumerate(
+                (self.range_bins, self.vel_bins, np.cos(self.angle_bins), np.sin(self.angle_bins))))
+            for buf, t in zip(tabs, (self.range_bins, self.vel_bins, np.cos(self.angle_bins), np.sin(self.angle_bins))):
+                buf.upload(np.ascontiguousarray(t, dtype=np.float64))
+            self._pc_tables = tabs
+        self.d_points = self.bufs.get("points", max(F, 1) * cap * 32)
+        d_az, d_el = (self.d_az if self.az else None), (self.d_el if self.el else None)
+        for f0 in range(0, F, 32768):
+            _lib.check(self.ctx.lib.mmw_point_cloud(
+                self.ctx.handle, self.d_dets.at(f0 * cap * 8), self.d_cnt.at(f0 * 4), d_az.at(f0 * cap * 4) if d_az else None,
+                d_el.at(f0 * cap * 4) if d_el else None, tabs[0].ptr, tabs[1].ptr, tabs[2].ptr, tabs[3].ptr,
+                self.d_points.at(f0 * cap * 32), min(32768, F - f0), cap, len(self.range_bins), len(self.vel_bins), self.A))
+        self._points_cnt = self.d_cnt
+        return self.d_points
+
+    def fetch_point_clouds(self) -> List[np.ndarray]:
+        """The buffer of ``point_clouds_device()`` as per-frame ``(N, 4)`` arrays."""
+        pts = self.d_points.download((self.n_frames, self.cap, 4), np.float64)
+        return [pts[f, :n] if n else np.empty((0, 4)) for f, n in enumerate(self.counts)]
+
+    def _upload_points(self, point_clouds: Sequence[np.ndarray]) -> Tuple[int, np.ndarray]:
+        """Caller-made point clouds in place of the detector's: packed into the ``[F, cap, 4]`` buffer (the loaded cubes and
+        their detections are left alone).  Returns the frame count and the point counts."""
+        F, cap = len(point_clouds), self.cap
+        if F > self.max_frames:
+            raise ValueError("more point clouds than max_frames")
+        counts = np.array([len(p) for p in point_clouds], dtype=np.int32)
+        if np.any(counts > cap):
+            raise _lib.MmwGpuError(f"a point cloud of {int(counts.max())} points exceeds det_capacity {cap}")
+        packed = np.zeros((max(F, 1), cap, 4))
+        for f, p in enumerate(point_clouds):
+            if len(p):
+                packed[f, :len(p)] = np.asarray(p, dtype=np.float64).reshape(-1, 4)
+        self.d_points = self.bufs.get("points", max(F, 1) * cap * 32)
+        self.d_points.upload(packed)
+        self._points_cnt = self.bufs.get("points_cnt", max(F, 1) * 4)
+        self._points_cnt.upload(counts)
+        return F, counts
+
+    def ego_fits(self, estimator, point_clouds: Optional[Sequence[np.ndarray]] = None, with_mask: bool = False):
+        """The per-frame RANSAC fits of ``estimator`` for every frame (``mmw_ego_velocity_ransac``): float64 ``[F, dim + 2]``
+        rows (coefficients, R^2 on the inliers, inlier share), dim = 2 for the ``standard`` array geometry and 3 for ``ods``;
+        zeros where the fit fails.  Frames the kernel flags (``ego_flags``, ``n_ego_flagged``: a decision within rounding of
+        scikit-learn's) are recomputed by the estimator's own scikit-learn fit.  Point clouds: those of
+        ``point_clouds_device()``, or the caller's ``point_clouds`` (``(N, 4)`` arrays).  Returns (fits, counts)."""
+        from .point_cloud_processing import ransac_tables as T
+        from .point_cloud_processing.vel_estimator import RESIDUAL_THRESHOLD
+        from .point_cloud_processing.vel_estimator import GEOMETRY_DIM
+        geometry = estimator.config_manager.array_geometry
+        if geometry not in GEOMETRY_DIM:
+            raise ValueError(f"ego velocity needs the standard or the ods array geometry, not {geometry!r}")
+        dim = GEOMETRY_DIM[geometry]
+        if point_clouds is None:
+            self.point_clouds_device()
+            F, counts = self.n_frames, self.counts
+        else:
+            F, counts = self._upload_points(point_clouds)
+        cap = self.cap
+        subsets, row, tab, offs = T.frame_tables(counts)
+        bufs, F1 = self.bufs, max(F, 1)
+        d_sub, d_row = bufs.get("ego_subsets", max(subsets.nbytes, 16)), bufs.get("ego_row", F1 * 4)
+        d_tab, d_off = bufs.get("ego_trials", tab.nbytes), bufs.get("ego_trials_off", max(offs.nbytes, 16))
+        for buf, arr in ((d_sub, subsets), (d_row, row), (d_tab, tab), (d_off, offs)):
+            if arr.size:
+                buf.upload(arr)
+        d_out, d_flags = bufs.get("ego_out", F1 * (dim + 2) * 8), bufs.get("ego_flags", F1 * 4)
+        d_mask = bufs.get("ego_mask", F1 * cap) if with_mask else None
+        for f0 in range(0, F, 32768):
+            _lib.check(self.ctx.lib.mmw_ego_velocity_ransac(
+                self.ctx.handle, self.d_points.at(f0 * cap * 32), self._points_cnt.at(f0 * 4), min(32768, F - f0), cap, dim,
+                RESIDUAL_THRESHOLD, float(estimator.min_R2_threshold), d_sub.ptr, d_row.at(f0 * 4), len(offs), d_tab.ptr, len(tab),
+                d_off.ptr, d_out.at(f0 * (dim + 2) * 8), d_flags.at(f0 * 4), d_mask.at(f0 * cap) if with_mask else None))
+        fits = d_out.download((F, dim + 2), np.float64).copy()
+        self.ego_flags = d_flags.download((F,), np.int32).copy()
+        self.ego_masks = d_mask.download((F, cap), np.uint8).copy().astype(bool) if with_mask else None
+        flagged = np.nonzero(self.ego_flags)[0]
+        self.n_ego_flagged = len(flagged)
+        fit = estimator.lsq_fit_ego_vel_ransac_points_2D if dim == 2 else estimator.lsq_fit_ego_vel_ransac_points_3D
+        for f in flagged.tolist():              # within rounding of a decision: scikit-learn itself decides
+            n = int(counts[f])
+            pts = self.d_points.download((n, 4), np.float64, f * cap * 32)
+            if with_mask:
+                from .point_cloud_processing.vel_estimator import ransac_fit
+                coef, r2, share, mask = ransac_fit(pts, dim, return_mask=True)
+                self.ego_masks[f, :n] = mask
+            else:
+                coef, r2, share = fit(points=pts)
+            fits[f] = 0.0
+            fits[f, :len(coef)] = coef
+            fits[f, dim:] = r2, share
+        return fits, counts
+
+    def ego_velocities(self, estimator, point_clouds: Optional[Sequence[np.ndarray]] = None) -> np.ndarray:
+        """``estimator.process(points=...)`` (a ``VelocityEstimator``) called on every frame's point cloud in order: float64
+        ``[F, 3]`` current velocity estimates.  The fits run on the device (``ego_fits``); the estimator's state (statistics,
+        proposal, current estimate) is advanced frame by frame on the host and carries across calls and ``stream()`` chunks."""
+        fits, counts = self.ego_fits(estimator, point_clouds)
+        return ego_state_scan(estimator, fits, counts)
+
+
+def ego_state_scan(estimator, fits: np.ndarray, counts: Sequence[int]) -> np.ndarray:
+    """``VelocityEstimator.process`` for every frame given the frames' fits (``[F, dim + 2]``) and point counts: an empty frame
+    leaves the statistics and the proposal of the last non-empty one in place, and every frame ends in the estimator's
+    threshold check.  A failed fit (inlier share 0) proposes what the estimator's fit functions return for it: zeros, a
+    2-vector under the ``ods`` geometry too."""
+    dim = fits.shape[1] - 2
+    out = np.empty((len(counts), 3))
+    for f, n in enumerate(counts):
+        if n > 0:
+            share = fits[f, dim + 1]
+            estimator.take_fit(dim, (fits[f, :dim].copy() if share > 0 else np.zeros(2), float(fits[f, dim]), share))
+        estimator.update_and_check_current_vel_measurements()
+        out[f] = estimator.current_velocity_estimate
+    return out
 
 
 class MultiDeviceFramePipeline:
@@ -676,6 +816,18 @@ class MultiDeviceFramePipeline:
         self.dets = self._join([p.dets for p in live])
         self.n_refined = sum(p.n_refined for p in live)
         return pcs
+
+    def ego_velocities(self, estimator) -> np.ndarray:
+        """``FramePipeline.ego_velocities``: every device fits the frames of its shard (``ego_fits``), the estimator's state
+        runs once over the joined fits in frame order."""
+        live = [r for r in range(self.world) if self.bounds[r][1] > self.bounds[r][0]]
+        per_rank = self._each(lambda r: self.parts[r].ego_fits(estimator))
+        fits = np.concatenate([f for f, _ in per_rank]) if per_rank else np.empty((0, 4))
+        counts = np.concatenate([c for _, c in per_rank]) if per_rank else np.empty(0, dtype=np.int32)
+        if len(counts) != self.n_frames:
+            raise RuntimeError(f"joined {len(counts)} per-frame fits for {self.n_frames} frames")
+        self.n_ego_flagged = sum(getattr(self.parts[r], "n_ego_flagged", 0) for r in live)
+        return ego_state_scan(estimator, fits, counts)
 
     def chain3d(self, magnitude: bool = False, out: Optional[np.ndarray] = None) -> Optional[np.ndarray]:
         """3-D windowed FFT of every frame on its device.  ``out`` (optional, caller-owned ``[F, A, S, C]`` complex64 /

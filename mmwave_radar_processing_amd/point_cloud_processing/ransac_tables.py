@@ -1,0 +1,103 @@
+"""Host-made tables of the batched ego-velocity kernel (``mmw_ego_velocity_ransac``).
+
+Everything random or transcendental in scikit-learn's RANSAC loop is a function of the point count N alone, so it is evaluated
+here once per N (and kept for the life of the process) and the kernel only looks it up:
+
+* ``subset_table(N)``: the 20 x 10 indices ``RANSACRegressor(random_state=42, min_samples=10, max_trials=20).fit`` draws for N
+  samples -- a fresh ``RandomState(42)`` per fit, one ``sample_without_replacement(N, 10)`` per trial, skipped or not;
+* ``trials_table(N)``: ``min(20, _dynamic_max_trials(k, N, 10, 0.99))`` for k = 0 .. N inliers.
+"""
+from __future__ import annotations
+
+from typing import Dict, Sequence, Tuple
+
+import numpy as np
+
+from .._lazy import lazy_import
+
+MIN_SAMPLES = 10
+MAX_TRIALS = 20
+STOP_PROBABILITY = 0.99
+SEED = 42
+_EPSILON = np.spacing(1)
+
+_subsets: Dict[int, np.ndarray] = {}
+_trials: Dict[int, np.ndarray] = {}
+
+
+def subset_table(n: int) -> np.ndarray:
+    n = int(n)
+    tab = _subsets.get(n)
+    if tab is None:
+        if n < MIN_SAMPLES:
+            raise ValueError(f"no {MIN_SAMPLES}-point subset of {n} points")
+        draw = lazy_import("sklearn.utils.random").sample_without_replacement
+        rs = np.random.RandomState(SEED)
+        tab = np.array([draw(n, MIN_SAMPLES, random_state=rs) for _ in range(MAX_TRIALS)], dtype=np.int32)
+        tab.setflags(write=False)
+        _subsets[n] = tab
+    return tab
+
+
+def dynamic_max_trials(n_inliers, n_samples: int) -> float:
+    """scikit-learn 1.7.2 ``_dynamic_max_trials(n_inliers, n_samples, 10, 0.99)``: the same NumPy scalar expression."""
+    inlier_ratio = n_inliers / float(n_samples)
+    nom = max(_EPSILON, 1 - STOP_PROBABILITY)
+    denom = max(_EPSILON, 1 - inlier_ratio ** MIN_SAMPLES)
+    if nom == 1:
+        return 0
+    if denom == 1:
+        return float("inf")
+    return abs(float(np.ceil(np.log(nom) / np.log(denom))))
+
+
+def trials_table(n: int) -> np.ndarray:
+    """int32 ``[n + 1]``.  Evaluated from k = n downwards; the value grows as k falls, and once eight consecutive k have
+    reached the cap of 20 the rest is 20 (``trials_table_full`` evaluates every k; the tests compare the two)."""
+    n = int(n)
+    tab = _trials.get(n)
+    if tab is None:
+        tab = np.full(n + 1, MAX_TRIALS, dtype=np.int32)
+        run = 0
+        for k in range(n, -1, -1):
+            v = min(float(MAX_TRIALS), dynamic_max_trials(np.int64(k), n))
+            tab[k] = int(v)
+            run = run + 1 if v >= MAX_TRIALS else 0
+            if run >= 8:
+                break
+        tab.setflags(write=False)
+        _trials[n] = tab
+    return tab
+
+
+def trials_table_full(n: int) -> np.ndarray:
+    return np.array([int(min(float(MAX_TRIALS), dynamic_max_trials(np.int64(k), n))) for k in range(int(n) + 1)], dtype=np.int32)
+
+
+def seed_tables(n: int, subsets: np.ndarray, trials: np.ndarray) -> None:
+    """Install recorded tables for N = n (a host without scikit-learn driving the kernel from stored draws)."""
+    subsets = np.ascontiguousarray(subsets, dtype=np.int32)
+    trials = np.ascontiguousarray(trials, dtype=np.int32)
+    if subsets.shape != (MAX_TRIALS, MIN_SAMPLES) or trials.shape != (int(n) + 1,) or subsets.min() < 0 or subsets.max() >= n:
+        raise ValueError(f"tables do not fit N = {n}")
+    _subsets[int(n)], _trials[int(n)] = subsets, trials
+
+
+def frame_tables(counts: Sequence[int]) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The four table arguments of ``mmw_ego_velocity_ransac`` for a batch with these point counts:
+    ``subsets [R, 20, 10]``, ``subset_row [F]`` (-1 below 10 points), ``trials_tab``, ``trials_off [R]``."""
+    counts = np.asarray(counts, dtype=np.int64)
+    sizes = np.unique(counts[counts >= MIN_SAMPLES])
+    row = np.full(counts.shape, -1, dtype=np.int32)
+    subsets = np.zeros((max(len(sizes), 1), MAX_TRIALS, MIN_SAMPLES), dtype=np.int32)
+    offs = np.zeros(max(len(sizes), 1), dtype=np.int32)
+    tabs, off = [], 0
+    for r, n in enumerate(sizes.tolist()):
+        subsets[r] = subset_table(n)
+        t = trials_table(n)
+        offs[r] = off
+        tabs.append(t)
+        off += len(t)
+        row[counts == n] = r
+    tab = np.concatenate(tabs) if tabs else np.zeros(1, dtype=np.int32)
+    return subsets[:len(sizes)] if len(sizes) else subsets[:0], row, tab, offs[:len(sizes)]

@@ -146,6 +146,15 @@ def main():
         ctx.handle, d_in.ptr, d_l1.ptr, d_rd.ptr, d_dets.ptr, d_cnt.ptr, d_idx.ptr, min(F, 32768), V, S, C, cap, ants, n_ant,
         A, 1, None)), F * 76 * n_ant * 8)
     res["mean_detections_per_frame"] = float(d_cnt.download((F,), np.int32).mean())
+    # ---- device point clouds of those detections (angle bins of the exact argmax as azimuth, no elevation list)
+    Fp = min(F, 32768)
+    tabs = [ctx.alloc(n * 8) for n in (S, C, A, A)]
+    for t, n in zip(tabs, (S, C, A, A)):
+        t.upload(np.linspace(0.0, 1.0, n))
+    d_pts = ctx.alloc(Fp * cap * 32)
+    run("point_cloud", lambda: _lib.check(L.mmw_point_cloud(ctx.handle, d_dets.ptr, d_cnt.ptr, d_idx.ptr, None, tabs[0].ptr,
+                                                            tabs[1].ptr, tabs[2].ptr, tabs[3].ptr, d_pts.ptr, Fp, cap, S, C, A)),
+        Fp * cap * (8 + 4 + 32))
     # ---- Doppler-azimuth: coarse (3-D chain + range mean) and precise (zoom transform, 2 x 128 bins) modes
     Fz = min(F, 256)
     d_mag3 = ctx.alloc(Fz * A * S * C * 4)
