@@ -360,7 +360,17 @@ int mmw_detect_points(mmw_ctx *ctx, const void *d_cubes, void *d_rd, float *d_l1
  *   (mmw_detect_points uses the worst-case bound throughout.)
  *   h_n_refined (may be NULL): number of re-evaluated detections; passing it makes the call synchronise.
  * mmw_angle_argmax_cells64: the float64 angle DFT + first-max argmax for rows of n_ant complex128 cells the caller
- *   gathered itself (a caller-supplied complex128 range-Doppler cube, :168-178); d_cells [n_rows][n_ant]. */
+ *   gathered itself (a caller-supplied complex128 range-Doppler cube, :168-178); d_cells [n_rows][n_ant].
+ * mmw_rd_cells64_at: the complex128 range-Doppler cells the float64 re-evaluation of mmw_angle_argmax_exact works on, read
+ *   out for tests: d_out[F][cap][n_ant] complex128 = cell (r, fftshifted Doppler index) of antenna h_ant[i] for every listed
+ *   detection (slots from min(d_counts[f], cap) on are left as they were) -- the values the reference's
+ *   PointCloudGenerator._compute_angle_estimation gathers from its complex128 cube (processors/point_cloud_generator.py:168-178;
+ *   the cube: RangeDopplerProcessor.process, processors/range_doppler_resp.py:49-110).  route = MMW_CELLS64_DENSE: the kernel of the dense refinement (one Doppler FFT per
+ *   sample row + range sums; 128 chirps and at most 829 samples, MMW_ERR_UNSUPPORTED otherwise); MMW_CELLS64_DIRECT: the
+ *   plane slices of the direct refinement, added in the order the refinement adds them (any plane).  Synchronises (d_out is complete at return); a
+ *   listed detection outside the plane is MMW_ERR_INVALID. */
+#define MMW_CELLS64_DENSE  0
+#define MMW_CELLS64_DIRECT 1
 int mmw_angle_argmax(mmw_ctx *ctx, const void *d_rd, const int32_t *d_dets, const int32_t *d_counts,
                      int32_t *d_idx, int n_frames, int V, int S, int C, int cap,
                      const int *h_ant, int n_ant, int A, int shift);
@@ -371,6 +381,8 @@ int mmw_angle_argmax_exact(mmw_ctx *ctx, const void *d_cubes, const float *d_l1,
                            int *h_n_refined);
 int mmw_angle_argmax_cells64(mmw_ctx *ctx, const void *d_cells, int32_t *d_idx, int n_rows, int n_ant, int A,
                              int shift);
+int mmw_rd_cells64_at(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_dets, const int32_t *d_counts, void *d_out,
+                      int n_frames, int V, int S, int C, int cap, const int *h_ant, int n_ant, int route);
 
 /* ---------------------------------------------------------------- beamformers
  * mmw_bartlett: delay-and-sum steering-matrix contraction on MFMA for a batch of frames,

@@ -26,6 +26,7 @@ ABI_VERSION = 7          # include/mmwgpu.h MMWGPU_ABI_VERSION: the argtypes bel
 CFAR_CA, CFAR_OS, CFAR_GO, CFAR_SO = 0, 1, 2, 3
 ANGLE_MAGNITUDE, ANGLE_NO_WINDOW, ANGLE_NO_SHIFT = 1, 2, 4
 QUEUE_COMPUTE, QUEUE_COPY = 0, 1
+CELLS64_DENSE, CELLS64_DIRECT = 0, 1
 
 
 class MmwGpuError(RuntimeError):
@@ -100,6 +101,7 @@ _SIGNATURES = {
     "mmw_plane_l1": [_vp, _vp, _vp, _i, _i, _i, _i],
     "mmw_angle_argmax_exact": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _i, _i, _ip],
     "mmw_angle_argmax_cells64": [_vp, _vp, _vp, _i, _i, _i, _i],
+    "mmw_rd_cells64_at": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _i],
     "mmw_bartlett": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d],
     "mmw_capon": [_vp, _vp, C.POINTER(_d), _vp, _i, _i, _i, _i, _i, _d],
     "mmw_abs_c64": [_vp, _vp, _vp, _sz],

@@ -776,6 +776,18 @@ __global__ __launch_bounds__(256) void k_argmax_refine_finish(RefineArgs a) {
     }
 }
 
+// Read-out of the cells themselves (mmw_rd_cells64_at): the slices k_argmax_refine_part left, added in the order
+// k_argmax_refine_finish adds them, to cells[list[e]][i] instead of into an argmax.  One thread per (entry, antenna).
+__global__ __launch_bounds__(256) void k_refine_cells_sum(RefineArgs a, cplx<double> *cells, int n) {
+    const int stride = refine_stride(a);
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const int e = (int)(t / a.ants.n), i = (int)(t - (long)e * a.ants.n);
+    if (e >= n) return;
+    cplx<double> s = cplx<double>{0.0, 0.0};
+    for (int p = 0; p < a.parts; ++p) s = s + a.partial[((long)e * a.parts + p) * stride + i];
+    cells[(long)(a.list[e] & 0x7fffffff) * a.ants.n + i] = s;
+}
+
 __global__ __launch_bounds__(256) void k_argmax_refine_whole(RefineArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ cplx<double> red[4][REFINE_NA];

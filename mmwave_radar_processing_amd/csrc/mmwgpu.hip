@@ -1848,19 +1848,26 @@ static int rd_error_ulps(int S, int C) {
     return ulps;
 }
 
+// The launch of k_argmax_refine_part, shared by the refinement and by the read-out of its slices (mmw_rd_cells64_at): `units`
+// workgroups per slice walk the entries of the list.
+static int launch_refine_part(mmw_ctx *ctx, const RefineArgs &ra, int units) {
+    const size_t lds = refine_tabs_lds(ra.S, ra.C);
+    MMW_REQUIRE(lds <= 150 * 1024, "plane %d x %d too large for the refinement tables", ra.S, ra.C);
+    if (lds > 48 * 1024)
+        MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_argmax_refine_part), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_argmax_refine_part, dim3(ra.parts, units), dim3(256), lds, ctx->stream, ra);
+    return check_launch("argmax_refine_part");
+}
+
 // float64 re-evaluation of the detections k_angle_argmax flagged (ra.n_flag / ra.list): fixed grids, the flagged count
 // stays on the device, workgroups beyond it leave at once.  ra.partial must hold n_split * REFINE_PARTS * ants.n entries.
 static int launch_argmax_refine(mmw_ctx *ctx, const RefineArgs &ra) {
     const size_t lds = refine_tabs_lds(ra.S, ra.C);
     MMW_REQUIRE(lds <= 150 * 1024, "plane %d x %d too large for the refinement tables", ra.S, ra.C);
-    if (lds > 48 * 1024) {
-        MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_argmax_refine_part), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 48 * 1024)
         MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_argmax_refine_whole), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
     if (ra.n_split > 0) {
-        const int units = std::min(ra.n_split, std::max(1, 512));
-        hipLaunchKernelGGL(k_argmax_refine_part, dim3(ra.parts, units), dim3(256), lds, ctx->stream, ra);
-        MMW_TRY(check_launch("argmax_refine_part"));
+        MMW_TRY(launch_refine_part(ctx, ra, std::min(ra.n_split, 512)));
         hipLaunchKernelGGL(k_argmax_refine_finish, dim3(std::min((ra.n_split + 3) / 4, ctx->num_cu)), dim3(256), 0, ctx->stream, ra);
         MMW_TRY(check_launch("argmax_refine_finish"));
     }
@@ -1900,6 +1907,34 @@ static int fill_refine_args(mmw_ctx *ctx, RefineArgs *ra, const void *d_cubes, c
     ra->twC = (const cplx<double> *)twC64;
     ra->twA = (const cplx<double> *)twA64;
     return MMW_OK;
+}
+
+// The launch of k_cells64<128> (mmw_cells64.h), shared by the dense refinement and by the read-out of its cells
+// (mmw_rd_cells64_at): tables from the RefineArgs of the same call, one workgroup per (antenna of the list, frame).
+static int launch_cells64(mmw_ctx *ctx, const RefineArgs &ra, const int32_t *d_counts, const int *d_flagpos, int dense_min,
+                          cplx<double> *d_cells, int n_frames, int max_cells) {
+    Cells64Args ca{};
+    ca.cubes = ra.cubes;
+    ca.dets = ra.dets;
+    ca.counts = d_counts;
+    ca.flagpos = d_flagpos;
+    ca.n_flag = ra.n_flag;
+    ca.dense_min = dense_min;
+    ca.out = d_cells;
+    ca.V = ra.V;
+    ca.S = ra.S;
+    ca.cap = ra.cap;
+    ca.n_ant = ra.ants.n;
+    ca.max_cells = max_cells;
+    ca.ants = ra.ants;
+    ca.ws = ra.ws;
+    ca.wc = ra.wc;
+    ca.twS = ra.twS;
+    ca.twC = ra.twC;
+    const size_t lds = cells64_lds(ra.S, ra.C, max_cells);
+    MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cells64<128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_cells64<128>, dim3((unsigned)ra.ants.n, (unsigned)n_frames), dim3(C64_NT), lds, ctx->stream, ca);
+    return check_launch("cells64");
 }
 
 // The worst-case bound assumes every rounding error of every partial sum lines up; measured float32 errors stay below
@@ -1965,28 +2000,7 @@ int mmw_angle_argmax_exact(mmw_ctx *ctx, const void *d_cubes, const float *d_l1,
     ra.dense_min = dense_min;
     ra.dense_cap = dense_cap;
     if (dense_min > 0) {
-        Cells64Args ca{};
-        ca.cubes = (const float2 *)d_cubes;
-        ca.dets = d_dets;
-        ca.counts = d_counts;
-        ca.flagpos = d_flagpos;
-        ca.n_flag = d_nflag;
-        ca.dense_min = dense_min;
-        ca.out = d_cells;
-        ca.V = V;
-        ca.S = S;
-        ca.cap = cap;
-        ca.n_ant = n_ant;
-        ca.max_cells = max_cells;
-        ca.ants = ants;
-        ca.ws = ra.ws;
-        ca.wc = ra.wc;
-        ca.twS = ra.twS;
-        ca.twC = ra.twC;
-        const size_t lds = cells64_lds(S, C, max_cells);
-        MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cells64<128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_cells64<128>, dim3((unsigned)n_ant, (unsigned)n_frames), dim3(C64_NT), lds, ctx->stream, ca);
-        MMW_TRY(check_launch("cells64"));
+        MMW_TRY(launch_cells64(ctx, ra, d_counts, d_flagpos, dense_min, d_cells, n_frames, max_cells));
         Argmax64ListArgs la{d_cells, d_nflag, d_list, dense_min, dense_cap, n_ant, A, shift, d_idx, ra.twA};
         hipLaunchKernelGGL(k_argmax64_list, dim3((unsigned)std::min(std::max(dense_cap / 4, 1), 4 * ctx->num_cu)), dim3(256), 0, ctx->stream, la);
         MMW_TRY(check_launch("argmax64_list"));
@@ -2539,6 +2553,66 @@ int mmw_angle_argmax_cells64(mmw_ctx *ctx, const void *d_cells, int32_t *d_idx, 
     hipLaunchKernelGGL(k_argmax64_cells, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, ctx->stream,
                        (const cplx<double> *)d_cells, d_idx, n_rows, n_ant, A, shift, (const cplx<double> *)twA64);
     return check_launch("argmax64_cells");
+}
+
+// The float64 range-Doppler cells behind the exact argmax, read out: the dense route is k_cells64<128> itself with every listed
+// detection marked flagged (list position f * cap + det, so its output array IS d_out), the direct route the slices of
+// k_argmax_refine_part added in k_argmax_refine_finish's order.  A test entry: it synchronises and validates the list on the host.
+int mmw_rd_cells64_at(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_dets, const int32_t *d_counts, void *d_out, int n_frames,
+                      int V, int S, int C, int cap, const int *h_ant, int n_ant, int route) {
+    MMW_REQUIRE(ctx && d_cubes && d_dets && d_counts && d_out, "null argument");
+    MMW_JOIN(ctx);
+    MMW_REQUIRE(n_frames >= 0 && n_frames <= 65535 && V > 0 && S > 0 && S <= 65535 && C > 0 && cap >= 0, "bad shape");
+    MMW_REQUIRE((long)n_frames * cap < (1L << 31), "too many detection slots for one call");
+    MMW_REQUIRE(route == MMW_CELLS64_DENSE || route == MMW_CELLS64_DIRECT, "route must be MMW_CELLS64_DENSE or MMW_CELLS64_DIRECT");
+    AntList ants{};
+    MMW_TRY(fill_ant_list(h_ant, n_ant, V, MAX_ANT, &ants));
+    const int max_cells = C == 128 ? cells64_max_cells(S, C) : 0;
+    if (route == MMW_CELLS64_DENSE && max_cells == 0)
+        return set_error(MMW_ERR_UNSUPPORTED, "no dense float64 cell kernel for %d x %d planes", S, C);
+    if (n_frames == 0 || cap == 0) return MMW_OK;
+    const int list_cap = n_frames * cap;
+    std::vector<int32_t> counts(n_frames), dets((size_t)list_cap * 2);
+    MMW_HIP(hipMemcpyAsync(counts.data(), d_counts, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MMW_HIP(hipMemcpyAsync(dets.data(), d_dets, dets.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MMW_HIP(hipStreamSynchronize(ctx->stream));
+    // words 0 .. 63: the count; then the list (direct: the listed slots in order; dense: flagpos[F][cap])
+    std::vector<int> host(64 + (size_t)list_cap, 0);
+    int n = 0;
+    for (int f = 0; f < n_frames; ++f)
+        for (int det = 0; det < std::min(std::max(counts[f], 0), cap); ++det) {
+            const int slot = f * cap + det, r = dets[2 * (size_t)slot], d = dets[2 * (size_t)slot + 1];
+            MMW_REQUIRE(r >= 0 && r < S && d >= 0 && d < C, "detection %d of frame %d lies outside the %d x %d plane", det, f, S, C);
+            if (route == MMW_CELLS64_DENSE) host[64 + slot] = slot + 1;
+            else host[64 + n] = slot;
+            ++n;
+        }
+    if (n == 0) return MMW_OK;
+    host[0] = route == MMW_CELLS64_DENSE ? list_cap : n;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const int parts = refine_parts(n_frames);
+    const size_t list_bytes = up(host.size() * sizeof(int));
+    const size_t part_bytes = route == MMW_CELLS64_DIRECT ? up((size_t)n * parts * n_ant * sizeof(cplx<double>)) : 0;
+    MMW_TRY(ensure_scratch(ctx, list_bytes + part_bytes));
+    int *d_nflag = (int *)ctx->scratch, *d_list = d_nflag + 64;
+    MMW_HIP(hipMemcpyAsync(d_nflag, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    MMW_HIP(hipStreamSynchronize(ctx->stream));       // (`host` is pageable and leaves scope on every return below)
+    RefineArgs ra{};
+    MMW_TRY(fill_refine_args(ctx, &ra, d_cubes, d_dets, d_nflag, d_list, n, n, (cplx<double> *)((char *)ctx->scratch + list_bytes),
+                             n_frames, V, S, C, cap, MAX_ANT));
+    ra.ants = ants;
+    int rc = MMW_OK;
+    if (route == MMW_CELLS64_DENSE) {
+        rc = launch_cells64(ctx, ra, d_counts, d_list, 1, (cplx<double> *)d_out, n_frames, max_cells);
+    } else {
+        MMW_TRY(launch_refine_part(ctx, ra, std::min(n, 512)));
+        hipLaunchKernelGGL(k_refine_cells_sum, dim3((unsigned)(((long)n * n_ant + 255) / 256)), dim3(256), 0, ctx->stream, ra,
+                           (cplx<double> *)d_out, n);
+        rc = check_launch("refine_cells_sum");
+    }
+    MMW_TRY(rc);
+    MMW_HIP(hipStreamSynchronize(ctx->stream));       // a test entry: d_out is complete at return
+    return MMW_OK;
 }
 
 int mmw_abs_c64(mmw_ctx *ctx, const void *d_in, float *d_out, size_t n) {

@@ -185,7 +185,7 @@ def test_exact_argmax_refinement_paths(monkeypatch):
     pipe = FramePipeline(cm, max_frames=3, shape=(12, 256, 128), az_antenna_idxs=az, el_antenna_idxs=el)
     pipe.load(cubes)
     n_dets = sum(r[1].shape[0] for r in refs)
-    for div, split, expect_all in (("1", None, False), ("8", None, False), ("1", "0", False), ("1", "3", False)):
+    for div, split in (("1", None), ("8", None), ("1", "0"), ("1", "3")):
         monkeypatch.setenv("MMW_ARGMAX_BOUND_DIV", div)
         if split is None:
             monkeypatch.delenv("MMW_REFINE_SPLIT", raising=False)
@@ -200,6 +200,37 @@ def test_exact_argmax_refinement_paths(monkeypatch):
         assert 0 <= pipe.n_refined < n_dets
     monkeypatch.delenv("MMW_REFINE_SPLIT", raising=False)
     monkeypatch.delenv("MMW_ARGMAX_BOUND_DIV", raising=False)
+    # every detection through the float64 path: the strong component of tests/refine_cases.py in antennas 1 .. 11 raises the
+    # bound (the plane norms) while the detector, which reads antenna 0 alone, lists noise-level cells (OS-CFAR: the
+    # stand-alone mmw_angle_argmax_exact); split-plane kernels, whole-plane kernels and both in one call
+    import refine_cases as rc
+    flagged = rc.make_cube(9100, 2, 12, 256, 128)
+    flagged[:, 0] = rc.make_cube(9101, 2, 1, 256, 128, 0.0)[:, 0]
+    pipe = FramePipeline(cm, max_frames=2, shape=(12, 256, 128), cfar=OsCFAR2D((5, 5), (3, 2), rho=0.7, alpha=2.0),
+                         az_antenna_idxs=az, el_antenna_idxs=el)
+    pipe.load(flagged)
+    assert not pipe._fused_supported(True)
+    dets_ref = [O.rd_detect_2d_os(c) for c in flagged]
+    n_dets = sum(len(d) for d in dets_ref)
+    allowed = rc.allowed_cells(256, 128)
+    assert n_dets > 500 and all(np.all(allowed[d[:, 0], d[:, 1]]) for d in dets_ref), "a detection on the strong component"
+    for split in (None, "0", "3"):
+        if split is None:
+            monkeypatch.delenv("MMW_REFINE_SPLIT", raising=False)
+        else:
+            monkeypatch.setenv("MMW_REFINE_SPLIT", split)
+        pipe.point_clouds()
+        assert pipe.n_refined == 2 * n_dets, f"{pipe.n_refined} of {2 * n_dets} evaluations refined with P_TONE = {rc.P_TONE:g}"
+        for f, d in enumerate(dets_ref):
+            np.testing.assert_array_equal(pipe.dets[f], d)
+            raw = O.range_doppler(flagged[f])
+            for got, ants, shift in ((pipe.az_idx[f], az, True), (pipe.el_idx[f], el, False)):
+                want, resp = O.angle_argmax(raw, d[:, 0], d[:, 1], ants, 64, shift)
+                top = np.sort(resp, axis=1)[:, -2:]
+                sure = top[:, 1] - top[:, 0] >= rc.MARGIN_MIN * top[:, 1]
+                assert np.count_nonzero(~sure) <= 0.01 * len(d)
+                np.testing.assert_array_equal(got[sure], want[sure])
+    monkeypatch.delenv("MMW_REFINE_SPLIT", raising=False)
     # float64 cell path: NaN wins and the first one is reported; +inf beats finite values
     ctx = _lib.default_context()
     cells = np.zeros((3, 4), dtype=np.complex128)
