@@ -159,6 +159,22 @@ int mmw_chain3d_raw_i16(mmw_ctx *ctx, const void *d_raw_i16, void *d_rd, void *d
  *   nearest-bin index tables are computed by the host from its angle / velocity bin tables. */
 int mmw_dbs_gather(mmw_ctx *ctx, const float *d_mag, const int *h_ang_idx, const int *h_vel_idx, float *d_out,
                    int n_frames, int A, int S, int C, int n_out);
+/* mmw_dbs_sharpen: d_out[F][S][n_out] float32 = the Doppler-beam-sharpened range-azimuth image of every frame, each frame
+ *   with index tables of its own (frames of a recording move at different velocities):
+ *     rx = h_rx[n_rx] (n_rx == 0: all V antennas), n = len(rx), w = np.hanning(n),
+ *     b  = (h_ang_idx[f][i] - A/2) mod A      the FFT bin behind the fftshifted angle index,
+ *     k  = h_vel_idx[f][i]                    the fftshifted Doppler index, as mmw_range_doppler stores its cube,
+ *     d_out[f][s][i] = | sum_j w[j] RD[f][rx[j]][s][k] exp(-2 pi i j b / A) |,   RD = mmw_range_doppler(d_cubes).
+ *   This is |compute_3d_windowed_fft(cube[rx])|[h_ang_idx[f][i], s, h_vel_idx[f][i]] -- process_dbs_enhanced and
+ *   perform_dbs_sharpen (processors/range_angle_resp_dbs_enhanced.py:216-263,265-300: antenna subset first, Hann over the
+ *   subset, zero-pad to A) -- as a single-bin angle DFT per pixel: no [A][S][C] cube is allocated or written.  The tables
+ *   are host arrays [F][n_out] (the nearest-bin argmins of :240-257, made by the caller from its bin tables).
+ *   d_rd: NULL = the range-Doppler cubes pass through library scratch in chunks of frames, else [F][V][S][C] c64 to keep them.
+ *   MMW_ERR_INVALID (nothing launched) names the frame and entry of a table value outside [0, A) / [0, C), an rx outside
+ *   [0, V), n > 32, A < n, or n_frames * S * n_out beyond 2^31 - 1.  n_frames == 0 or n_out == 0: MMW_OK, nothing launched.
+ *   Profile family "dbs_sharpen" (the range-Doppler pass counts under "rd"). */
+int mmw_dbs_sharpen(mmw_ctx *ctx, const void *d_cubes, void *d_rd, const int32_t *h_ang_idx, const int32_t *h_vel_idx,
+                    float *d_out, int n_frames, int V, int S, int C, int A, const int *h_rx, int n_rx, int n_out);
 /* mmw_mean_over_range: d_out[F][C][A] float32 = mean over range rows [s_lo, s_hi) of d_mag[F][A][S][C];
  *   with mmw_chain3d(flags | MAGNITUDE) this is DopplerAzimuthProcessor.process, coarse path
  *   (processors/doppler_azimuth_resp.py:84-128,296-334,419-491): range FFT -> range-window mask ->

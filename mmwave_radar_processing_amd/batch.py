@@ -103,6 +103,74 @@ def ground_gates(range_bins: np.ndarray, altitudes_m: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(np.stack([near, far], axis=1), dtype=np.int32)
 
 
+DBS_TIE_MARGIN = 1e-9      # relative margin below which a batched nearest-bin / branch decision is re-made by the per-frame code
+
+
+def dbs_index_tables(dbs, velocities_ned: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """``dbs._dbs_indices(v)`` of every row ``v`` of ``velocities_ned`` at once: two int32 ``[F, n_out]`` tables (angle bin,
+    Doppler bin), identical to the per-frame function entry by entry.
+
+    The per-frame function takes ``np.dot`` of a normalised 3-vector per output angle and an argmin over ``vel_bins``
+    (reference: range_angle_resp_dbs_enhanced.py:200-214,239-255).  The batched restatement (one matrix product, a
+    ``searchsorted`` between the two neighbouring bins) may round a Doppler speed differently by a few ulps, which can only
+    change the answer where the speed sits within those ulps of the midpoint of two bins.  So every frame holding an entry whose
+    two candidate distances differ by less than ``DBS_TIE_MARGIN`` of the scale of the products summed into the speed (and of the
+    bins) -- seven decades above the rounding, however far the products cancel --
+    or that is not finite, is handed to ``_dbs_indices`` itself; so is everything when ``vel_bins`` is not strictly
+    increasing or holds fewer than two bins.  tests/test_dbs_batch_host.py holds the identity on midpoint, edge and random velocities."""
+    v = np.asarray(velocities_ned, dtype=np.float64).reshape(-1, 3)
+    ang = np.asarray(dbs.angle_bins_dbs_enhanced, dtype=np.float64)
+    bins = np.asarray(dbs.vel_bins, dtype=np.float64)
+    F, n_out = v.shape[0], ang.shape[0]
+    ang_row = np.argmin(np.abs(np.asarray(dbs.angle_bins_no_dbs_enhancement)[None, :] - ang[:, None]), axis=1)
+    ang_tab = np.ascontiguousarray(np.broadcast_to(ang_row.astype(np.int32), (F, n_out)))
+    vel_tab = np.zeros((F, n_out), dtype=np.int32)
+    if F == 0 or n_out == 0:
+        return ang_tab, vel_tab
+    if bins.size >= 2 and np.all(np.diff(bins) > 0):
+        r = np.stack([np.cos(ang), np.sin(ang), np.zeros_like(ang)], axis=1)
+        r = r / np.linalg.norm(r, axis=1, keepdims=True)
+        with np.errstate(invalid="ignore", over="ignore"):
+            dop = -(v @ r.T)                                               # [F, n_out]
+            hi = np.clip(np.searchsorted(bins, dop), 1, bins.size - 1)     # the two neighbours; bins 0, 1 / the last two
+            lo = hi - 1                                                    # beyond either end
+            d_lo, d_hi = np.abs(bins[lo] - dop), np.abs(bins[hi] - dop)
+            vel_tab[:] = np.where(d_lo <= d_hi, lo, hi)                    # argmin keeps the first of two equal distances
+            # the two roundings of a speed differ by ulps of its TERMS (|v_x cos| + |v_y sin|), which cancel in the speed itself
+            scale = np.maximum(np.max(np.abs(bins)), np.abs(v) @ np.abs(r.T))
+            sure = np.abs(d_lo - d_hi) > DBS_TIE_MARGIN * scale            # false for NaN
+        redo = np.flatnonzero(~np.all(sure, axis=1))
+    else:
+        redo = np.arange(F)
+    for f in redo:
+        vel_tab[f] = dbs._dbs_indices(v[f])[1]
+    return ang_tab, vel_tab
+
+
+def dbs_branches(dbs, velocities_ned: np.ndarray) -> np.ndarray:
+    """bool ``[F]``: the frames ``dbs.process`` sharpens, i.e. NOT ``np.linalg.norm(v[0:2]) < dbs.min_vel_dbs``
+    (range_angle_resp_dbs_enhanced.py:329).  Speeds within ``DBS_TIE_MARGIN`` of the limit, and non-finite ones, are decided by
+    that very expression frame by frame."""
+    v = np.asarray(velocities_ned, dtype=np.float64).reshape(-1, 3)
+    lim = float(dbs.min_vel_dbs)
+    with np.errstate(invalid="ignore", over="ignore"):
+        speed = np.sqrt(v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1])
+        sharp = ~(speed < lim)
+        sure = np.abs(speed - lim) > DBS_TIE_MARGIN * max(abs(lim), np.finfo(np.float64).tiny)
+    for f in np.flatnonzero(~sure):
+        sharp[f] = not (np.linalg.norm(v[f][0:2]) < lim)
+    return sharp
+
+
+def _runs(flags: np.ndarray):
+    """(start, stop, value) of every run of equal consecutive entries of a bool array."""
+    f0 = 0
+    for f in range(1, len(flags) + 1):
+        if f == len(flags) or flags[f] != flags[f0]:
+            yield f0, f, bool(flags[f0])
+            f0 = f
+
+
 class FramePipeline:
     """``[F, V, S, C]`` complex64 cubes in HBM -> RD cube, detections, point clouds, 3-D FFT cube.
 
@@ -318,6 +386,82 @@ class FramePipeline:
         if self._cube3d_mag:
             return self.d_cube3d.download((A, S, C), np.float32, frame * A * S * C * 4)
         return self.d_cube3d.download((A, S, C), np.complex64, frame * A * S * C * 8)
+
+    def _dbs_launch(self, dbs, velocities_ned, rx_antennas, chirp_idx, with_slow: bool = True):
+        """Argument checks, host tables and launches of ``dbs_range_angle`` / ``dbs_range_angle_device``; no download.
+        ``with_slow=False`` leaves the plain range-angle response of the slow frames out."""
+        from .processors.range_angle_resp_dbs_enhanced import RangeAngleProcessorDBSEnhanced
+        # every argument check comes before the first use of self.ctx / self.bufs (tests/test_dbs_batch_host.py calls this
+        # on a pipeline that has no device behind it)
+        if not isinstance(dbs, RangeAngleProcessorDBSEnhanced):
+            raise ValueError(f"dbs_range_angle: dbs must be a RangeAngleProcessorDBSEnhanced, got {type(dbs).__name__}")
+        F, V, S, C = self.n_frames, self.V, self.S, self.C
+        v = np.asarray(velocities_ned, dtype=np.float64)
+        if v.ndim != 2 or v.shape != (F, 3):
+            raise ValueError(f"dbs_range_angle: velocities_ned must be [{F}, 3] (one NED velocity per resident frame), got {v.shape}")
+        rx = np.asarray(rx_antennas).astype(int).ravel()
+        if np.any((rx < -V) | (rx >= V)):
+            raise ValueError(f"dbs_range_angle: rx_antennas {rx.tolist()} hold an index outside the {V} antennas")
+        A = int(dbs.num_angle_bins)
+        n = rx.size if rx.size else V
+        if A < n:
+            raise ValueError(f"dbs_range_angle: dbs.num_angle_bins ({A}) must be >= number of antennas ({n})")
+        n_out = int(len(dbs.angle_bins_dbs_enhanced))
+        sharp = dbs_branches(dbs, v)
+        ang_tab, vel_tab = dbs_index_tables(dbs, v[sharp])
+        self.dbs_sharpened = sharp
+        self._dbs_shape = (A, n_out)
+        self.d_dbs = self.bufs.get("dbs_out", max(F, 1) * S * max(n_out, 1) * 4)
+        with_slow = with_slow and not np.all(sharp)
+        d_ra = self.bufs.get("dbs_ra", int(np.count_nonzero(~sharp)) * S * A * 4) if with_slow else None
+        rx_pos, n_rx = _lib.int_array(rx % V)
+        rx_raw, _ = _lib.int_array(rx)
+        lib, h = self.ctx.lib, self.ctx.handle
+        done, slow_at = 0, {}
+        for f0, f1, fast in _runs(sharp):
+            cubes = self.d_in.at(f0 * self.cube_bytes)
+            if fast:
+                a_rows, v_rows = ang_tab[done:done + f1 - f0], vel_tab[done:done + f1 - f0]
+                done += f1 - f0
+                _lib.check(lib.mmw_dbs_sharpen(h, cubes, None, a_rows.ctypes.data_as(_lib._ip), v_rows.ctypes.data_as(_lib._ip),
+                                               self.d_dbs.at(f0 * S * n_out * 4), f1 - f0, V, S, C, A, rx_pos, n_rx, n_out))
+            elif with_slow:
+                slot = len(slow_at)
+                _lib.check(lib.mmw_range_angle(h, cubes, d_ra.at(slot * S * A * 4), f1 - f0, V, S, C, A, int(chirp_idx),
+                                               rx_raw, n_rx, 1))
+                slow_at.update({f: slot + f - f0 for f in range(f0, f1)})
+        return d_ra, slow_at
+
+    def dbs_range_angle(self, dbs, velocities_ned, rx_antennas=(), chirp_idx: int = 0) -> List[np.ndarray]:
+        """``dbs.process(cube_f, velocity_ned=velocities_ned[f], rx_antennas=..., chirp_idx=...)`` of every resident frame
+        (reference: range_angle_resp_dbs_enhanced.py:308-342, driven per frame by scripts/doppler_deam_sharpening_demo.py).
+
+        ``dbs``: a ``RangeAngleProcessorDBSEnhanced``; only its bin tables, ``num_angle_bins`` and ``min_vel_dbs`` are read.
+        ``velocities_ned``: ``[n_frames, 3]``, used as given (``ego_velocities()`` reports the sensor frame: the caller converts,
+        as the caller of the reference does).  Returns ``n_frames`` float64 arrays: ``[S, n_out]`` sharpened
+        (``mmw_dbs_sharpen``: a single-bin angle DFT per pixel on the batch's range-Doppler cubes, no ``[A, S, C]`` cube) where
+        the horizontal speed is not below ``dbs.min_vel_dbs``, else the plain ``[S, A]`` range-angle response of chirp
+        ``chirp_idx`` (``mmw_range_angle``, one call per run of consecutive slow frames).  ``self.dbs_sharpened`` (bool
+        ``[n_frames]``) says which.  The index tables of all frames are made at once by ``dbs_index_tables`` and equal
+        ``dbs._dbs_indices`` per frame.  The resident cubes are not changed."""
+        d_ra, slow_at = self._dbs_launch(dbs, velocities_ned, rx_antennas, chirp_idx)
+        F, S = self.n_frames, self.S
+        A, n_out = self._dbs_shape
+        out: List[np.ndarray] = [None] * F
+        for f0, f1, fast in _runs(self.dbs_sharpened):
+            if fast:
+                block = self.d_dbs.download((f1 - f0, S, n_out), np.float32, f0 * S * n_out * 4).astype(np.float64)
+            else:
+                block = d_ra.download((f1 - f0, S, A), np.float32, slow_at[f0] * S * A * 4).astype(np.float64)
+            for f in range(f0, f1):
+                out[f] = block[f - f0]
+        return out
+
+    def dbs_range_angle_device(self, dbs, velocities_ned, rx_antennas=(), chirp_idx: int = 0) -> _lib.DeviceBuffer:
+        """The sharpened images of ``dbs_range_angle`` left in HBM: float32 ``[n_frames][S][n_out]``, no download.  The rows of
+        frames below ``dbs.min_vel_dbs`` are NOT written (``self.dbs_sharpened`` says which frames they are)."""
+        self._dbs_launch(dbs, velocities_ned, rx_antennas, chirp_idx, with_slow=False)
+        return self.d_dbs
 
     def _alloc_detect(self):
         F, V, cap = self.n_frames, self.V, self.cap

@@ -5,6 +5,7 @@
 #include "mmw_ground.h"
 #include "mmw_seq.h"
 #include "mmw_misc.h"
+#include "mmw_dbs.h"
 #include "mmw_czt.h"
 #include "mmw_beamform.h"
 #include "mmw_detect.h"
@@ -670,6 +671,76 @@ int mmw_dbs_gather(mmw_ctx *ctx, const float *d_mag, const int *h_ang_idx, const
     hipLaunchKernelGGL(k_dbs_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_mag, d_idx,
                        d_idx + n_out, d_out, n_frames, A, S, C, n_out);
     return check_launch("dbs_gather");
+}
+
+// Frames per launch pair (range-Doppler, k_dbs_sharpen) when the range-Doppler cubes go to the library's scratch: as many as keep
+// the intermediate within MMW_DBS_CHUNK_MB.  The default of 1024 bounds the scratch at 1 GB, as mmw_doppler_azimuth does; measured
+// on 1250 frames of 12 x 256 x 128 (tools/dbs_batch.py) larger chunks are faster all the way: 32 MB 3.82 ms, 128 MB
+// 2.46 ms, 1024 MB 2.07 ms, one chunk 2.04 ms -- keeping the chunk inside the Infinity Cache buys nothing against fewer launches.
+static long dbs_chunk_frames(const mmw_ctx *ctx, size_t cube_bytes, int n_frames) {
+    const size_t budget = (size_t)std::max(1, opt_int(ctx, "MMW_DBS_CHUNK_MB", 1024)) << 20;
+    return std::max<long>(1, std::min<long>({(long)(budget / cube_bytes), 65535L, (long)n_frames}));
+}
+
+int mmw_dbs_sharpen(mmw_ctx *ctx, const void *d_cubes, void *d_rd, const int32_t *h_ang_idx, const int32_t *h_vel_idx,
+                    float *d_out, int n_frames, int V, int S, int C, int A, const int *h_rx, int n_rx, int n_out) {
+    MMW_REQUIRE(ctx, "ctx is null");
+    MMW_JOIN(ctx);
+    MMW_REQUIRE(n_frames >= 0 && V > 0 && S > 0 && C > 0 && A > 0 && n_out >= 0, "bad shape");
+    MMW_REQUIRE(n_rx >= 0 && (n_rx == 0 || h_rx), "bad rx list");
+    const int n = n_rx ? n_rx : V;
+    MMW_REQUIRE(n <= MAX_ANT, "antenna list of %d entries: at most %d", n, MAX_ANT);
+    MMW_REQUIRE(A >= n, "more antennas (%d) than angle bins (%d)", n, A);
+    for (int j = 0; j < n_rx; ++j)
+        MMW_REQUIRE(h_rx[j] >= 0 && h_rx[j] < V, "rx entry %d is %d: not an antenna of [0, %d)", j, h_rx[j], V);
+    if (n_frames == 0 || n_out == 0) return MMW_OK;
+    MMW_REQUIRE(d_cubes && h_ang_idx && h_vel_idx && d_out, "null argument");
+    MMW_REQUIRE((long)n_frames * S * n_out <= (long)INT_MAX, "%d frames of %d x %d pixels do not fit the kernel's 32-bit pixel index",
+                n_frames, S, n_out);
+    // (b_i, k_i) per frame and output: the FFT bin behind the fftshifted angle index, and the Doppler index as the cube stores it
+    std::vector<int2> tab((size_t)n_frames * n_out);
+    for (int f = 0; f < n_frames; ++f)
+        for (int i = 0; i < n_out; ++i) {
+            const size_t e = (size_t)f * n_out + i;
+            const int a = h_ang_idx[e], k = h_vel_idx[e];
+            MMW_REQUIRE(a >= 0 && a < A, "frame %d, entry %d: angle index %d is not in [0, %d)", f, i, a, A);
+            MMW_REQUIRE(k >= 0 && k < C, "frame %d, entry %d: Doppler index %d is not in [0, %d)", f, i, k, C);
+            tab[e] = make_int2(((a - A / 2) % A + A) % A, k);
+        }
+    DbsArgs da{};
+    da.V = V, da.S = S, da.C = C, da.A = A, da.n_out = n_out;
+    for (int j = 0; j < n; ++j) {       // np.hanning(n) over the SUBSET (process_dbs_enhanced :290-295); zero only at its two ends
+        const float w = (float)np_window(TAB_HANN, j, n);
+        if (w == 0.f) continue;
+        if (da.n_eff == 0) da.j0 = j;
+        da.ant[da.n_eff] = n_rx ? h_rx[j] : j;
+        da.w[da.n_eff++] = w;
+    }
+    MMW_TRY(get_table<float>(ctx, TAB_TWIDDLE, A, (const void **)&da.tw));
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t cube_bytes = (size_t)V * S * C * sizeof(float2), tab_bytes = up(tab.size() * sizeof(int2));
+    const long chunk = d_rd ? std::min(n_frames, 65535) : dbs_chunk_frames(ctx, cube_bytes, n_frames);
+    MMW_TRY(ensure_scratch(ctx, tab_bytes + (d_rd ? 0 : (size_t)chunk * cube_bytes)));
+    int2 *d_tab = (int2 *)ctx->scratch;
+    MMW_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
+    MMW_HIP(hipStreamSynchronize(ctx->stream));     // the table is host memory of this call
+    const bool tw_lds = (size_t)A * sizeof(float2) <= 32768;
+    const size_t lds = tw_lds ? (size_t)A * sizeof(float2) : 0;
+    const dim3 block(256);
+    for (long f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int nf = (int)std::min<long>(chunk, n_frames - f0);
+        char *rd = d_rd ? (char *)d_rd + (size_t)f0 * cube_bytes : (char *)ctx->scratch + tab_bytes;
+        MMW_TRY(range_doppler_impl(ctx, (const char *)d_cubes + (size_t)f0 * cube_bytes, rd, nullptr, nf, V, S, C));
+        ProfScope ps(ctx, "dbs_sharpen");
+        da.rd = (const float2 *)rd;
+        da.tab = d_tab + (size_t)f0 * n_out;
+        da.out = d_out + (size_t)f0 * S * n_out;
+        const dim3 grid((unsigned)(((long)S * n_out + 255) / 256), (unsigned)nf);
+        if (tw_lds) hipLaunchKernelGGL(k_dbs_sharpen<true>, grid, block, lds, ctx->stream, da);
+        else hipLaunchKernelGGL(k_dbs_sharpen<false>, grid, block, 0, ctx->stream, da);
+        MMW_TRY(check_launch("dbs_sharpen"));
+    }
+    return MMW_OK;
 }
 
 int mmw_mean_over_range(mmw_ctx *ctx, const float *d_mag, float *d_out, int n_frames, int A, int S, int C,
