@@ -387,6 +387,11 @@ int mmw_detect_points(mmw_ctx *ctx, const void *d_cubes, void *d_rd, float *d_l1
  *   listed detection outside the plane is MMW_ERR_INVALID. */
 #define MMW_CELLS64_DENSE  0
 #define MMW_CELLS64_DIRECT 1
+/* MMW_CELLS64_DENSE_MIXED: the dense kernel of the other chirp counts, k_cells64_mixed<C> (C = R1 R2: a register DFT of R1
+ *   points per lane, R2 lanes per row) -- the chirp counts mmw_diag_cells64_plan reports, and 128 as well so that it can be
+ *   compared with MMW_CELLS64_DENSE on one plane; MMW_ERR_UNSUPPORTED where it has no instantiation or the plane's tables
+ *   exceed the LDS.  MMW_CELLS64_DENSE keeps meaning the 128-chirp kernel only. */
+#define MMW_CELLS64_DENSE_MIXED 2
 int mmw_angle_argmax(mmw_ctx *ctx, const void *d_rd, const int32_t *d_dets, const int32_t *d_counts,
                      int32_t *d_idx, int n_frames, int V, int S, int C, int cap,
                      const int *h_ant, int n_ant, int A, int shift);
@@ -466,6 +471,13 @@ int mmw_diag_chain_plan_nodev(int num_cu, int raw, int n_frames, int V, int S, i
 int mmw_diag_detect_plan(int S, int C, int cfar_kind, int train_r, int train_d, int guard_r, int guard_d, int n_az,
                          int n_el, int A, int plan[8]);
 int mmw_diag_czt_runs(const double *h_freq, int M, int n_used, int *h_runs, int cap, int *n_runs);
+/* mmw_diag_cells64_plan: which dense float64 cell kernel the refinement of mmw_angle_argmax_exact has for an S x C plane (host
+ *   logic only, no device): plan[0] = 0 none (no instantiation for C, or the tables exceed 160 KiB - 512 B of LDS: the direct
+ *   sums serve the plane) | 1 k_cells64<128> | 2 k_cells64_mixed<C>; for 1 and 2 plan[1] = R1 (points per lane), [2] = R2 (lanes
+ *   per row; R1 R2 = C), [3] = rows per pass, [4] = dynamic LDS bytes, [5] = cells per chunk, [6] = LDS pitch in complex128
+ *   elements; plan[7] = 1 when MMW_CELLS64_DENSE_MIXED of mmw_rd_cells64_at serves the plane (also at C == 128).  Whether
+ *   mmw_angle_argmax_exact USES kind 2 is the context option MMW_ARGMAX_DENSE_MIXED. */
+int mmw_diag_cells64_plan(int S, int C, int plan[8]);
 
 /* ---------------------------------------------------------------- per-kernel timing hook for bench.py
  * Average duration (ms) of the most recent launch group of the named kernel family measured

@@ -26,7 +26,7 @@ ABI_VERSION = 7          # include/mmwgpu.h MMWGPU_ABI_VERSION: the argtypes bel
 CFAR_CA, CFAR_OS, CFAR_GO, CFAR_SO = 0, 1, 2, 3
 ANGLE_MAGNITUDE, ANGLE_NO_WINDOW, ANGLE_NO_SHIFT = 1, 2, 4
 QUEUE_COMPUTE, QUEUE_COPY = 0, 1
-CELLS64_DENSE, CELLS64_DIRECT = 0, 1
+CELLS64_DENSE, CELLS64_DIRECT, CELLS64_DENSE_MIXED = 0, 1, 2
 
 
 class MmwGpuError(RuntimeError):
@@ -110,6 +110,7 @@ _SIGNATURES = {
     "mmw_diag_membw": [_vp, _vp, _vp, _sz, _i, _i],
     "mmw_diag_mfma_peak": [_vp, _i, C.POINTER(_d)],
     "mmw_diag_rd_plan": [_i, _i, _i, _ip],
+    "mmw_diag_cells64_plan": [_i, _i, _ip],
     "mmw_diag_chain_plan": [_vp, _i, _i, _i, _i, _i, _i, _ip],
     "mmw_diag_chain_plan_nodev": [_i, _i, _i, _i, _i, _i, _i, _i, _ip],
     "mmw_diag_detect_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _ip],

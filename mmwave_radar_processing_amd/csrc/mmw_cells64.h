@@ -27,31 +27,11 @@
 #include "mmw_ctx.h"
 #include "mmw_misc.h"
 #include "mmw_bf16x3.h"
+#include "mmw_cells64_mixed.h"
 
 namespace mmw {
 
-struct Cells64Args {
-    const float2 *cubes;        // [F][V][S][C] input cube
-    const int32_t *dets;        // [F][cap][2] (range bin, fftshifted Doppler index)
-    const int32_t *counts;      // [F]
-    const int *flagpos;         // [F][cap]: 1 + position in the flagged list (0: not flagged, or beyond dense_cap)
-    const int *n_flag;          // flagged evaluations of the call
-    int dense_min;              // the dense form runs when *n_flag >= dense_min (the direct kernels when it is below)
-    cplx<double> *out;          // [dense_cap][n_ant] float64 cells of the flagged evaluations
-    int V, S, cap, n_ant, max_cells;
-    AntList ants;
-    const double *ws, *wc;      // np.hanning(S), np.hanning(C)
-    const cplx<double> *twS, *twC;
-};
-
-constexpr int C64_NT = 512, C64_ROWS = 64, C64_PITCH = 137, C64_CELLS = 256, C64_ITEMS = 8 * C64_CELLS / C64_NT;
-// LDS: the pass's spectra [64][137], W_S, both windows, the chunk's cells (r << 16 | FFT bin; list position), wave counts
-inline size_t cells64_lds(int S, int C, int) {
-    return ((size_t)C64_ROWS * C64_PITCH + S) * 16 + ((size_t)S + C) * 8 + (size_t)C64_CELLS * 8 + 64;
-}
-inline int cells64_max_cells(int S, int C) {        // cells per chunk of a frame (0: the plane's tables do not fit the LDS)
-    return C == 128 && cells64_lds(S, C, 0) <= 160 * 1024 - 512 ? C64_CELLS : 0;
-}
+// Cells64Args, the C64_* constants, cells64_lds / cells64_max_cells and the plan: mmw_cells64_mixed.h
 
 template <int C>
 __global__ __launch_bounds__(C64_NT) void k_cells64(Cells64Args a) {
@@ -333,6 +313,7 @@ __global__ __launch_bounds__(C64_NT) void k_rd_mag64_256x128(Rd64Args a) {
         __syncthreads();                                         // the LDS goes back to phase A
     }
 }
+
 
 // float64 angle DFT + first-maximum argmax of the flagged evaluations whose cells k_cells64 produced (one wave each)
 struct Argmax64ListArgs {

@@ -354,6 +354,13 @@ inline int tune_int(const char *name, int dflt) {
     return v;
 }
 
+// an antenna list of a call (kernel argument; here because translation units without mmw_misc.h pass it too)
+constexpr int MAX_ANT = 32;
+struct AntList {
+    int n;
+    int idx[MAX_ANT];
+};
+
 // per-context option (mmw_diag_set_option), else the process environment, else the default
 inline int opt_int(const mmw_ctx *ctx, const char *name, int dflt) {
     if (ctx) {

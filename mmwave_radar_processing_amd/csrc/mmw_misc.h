@@ -278,12 +278,6 @@ __global__ __launch_bounds__(256) void k_zoom_rows(const float2 *x, const float2
         if (row0 + r < total_rows) out[(row0 + r) * m + k] = acc[r];
 }
 
-constexpr int MAX_ANT = 32;
-struct AntList {
-    int n;
-    int idx[MAX_ANT];
-};
-
 // np.argmax order on magnitudes: a NaN beats everything that is not a NaN, the FIRST maximum wins
 template <typename T> __device__ __forceinline__ bool mag_gt(T a, T b) {
     if (a != a) return !(b != b);

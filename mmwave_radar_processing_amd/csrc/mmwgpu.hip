@@ -1980,10 +1980,11 @@ static int fill_refine_args(mmw_ctx *ctx, RefineArgs *ra, const void *d_cubes, c
     return MMW_OK;
 }
 
-// The launch of k_cells64<128> (mmw_cells64.h), shared by the dense refinement and by the read-out of its cells
-// (mmw_rd_cells64_at): tables from the RefineArgs of the same call, one workgroup per (antenna of the list, frame).
+// The launch of the dense cell kernel the plan names -- k_cells64<128> (mmw_cells64.h) or k_cells64_mixed<C> (mmw_cells64_mixed.h) --, shared by the
+// dense refinement and by the read-out of its cells (mmw_rd_cells64_at): tables from the RefineArgs of the same call, one
+// workgroup per (antenna of the list, frame).
 static int launch_cells64(mmw_ctx *ctx, const RefineArgs &ra, const int32_t *d_counts, const int *d_flagpos, int dense_min,
-                          cplx<double> *d_cells, int n_frames, int max_cells) {
+                          cplx<double> *d_cells, int n_frames, const Cells64Plan &plan) {
     Cells64Args ca{};
     ca.cubes = ra.cubes;
     ca.dets = ra.dets;
@@ -1996,17 +1997,23 @@ static int launch_cells64(mmw_ctx *ctx, const RefineArgs &ra, const int32_t *d_c
     ca.S = ra.S;
     ca.cap = ra.cap;
     ca.n_ant = ra.ants.n;
-    ca.max_cells = max_cells;
+    ca.max_cells = plan.cells;
     ca.ants = ra.ants;
     ca.ws = ra.ws;
     ca.wc = ra.wc;
     ca.twS = ra.twS;
     ca.twC = ra.twC;
-    const size_t lds = cells64_lds(ra.S, ra.C, max_cells);
+    if (plan.kind == C64_KIND_MIXED) return launch_cells64_mixed(ctx, ca, ra.C, n_frames, plan.lds);
+    MMW_REQUIRE(plan.kind == C64_KIND_128, "no dense float64 cell kernel for %d x %d planes", ra.S, ra.C);
+    const size_t lds = cells64_lds(ra.S, ra.C, plan.cells);
     MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cells64<128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_cells64<128>, dim3((unsigned)ra.ants.n, (unsigned)n_frames), dim3(C64_NT), lds, ctx->stream, ca);
     return check_launch("cells64");
 }
+
+// MMW_ARGMAX_DENSE_MIXED: whether mmw_angle_argmax_exact uses k_cells64_mixed<C> where the plan has it (C != 128).  The default
+// is set by measurement (profiles/os_pipeline_np2.json).
+constexpr int ARGMAX_DENSE_MIXED_DEFAULT = 0;
 
 // The worst-case bound assumes every rounding error of every partial sum lines up; measured float32 errors stay below
 // 1.2 % of it (tests/argmax_margin.py: 68 000 evaluations on the 256 x 128 and 63 x 100 planes).
@@ -2039,8 +2046,11 @@ int mmw_angle_argmax_exact(mmw_ctx *ctx, const void *d_cubes, const float *d_l1,
     // Dense refinement (mmw_cells64.h): when many evaluations are flagged -- noise-level detections, e.g. the GUI's OS-CFAR --
     // the float64 cells of a whole frame come from one Doppler FFT per sample row + 256-term range sums instead of one
     // 32768-term sum per cell and antenna.  On when the call flags >= dense_min evaluations (8 per frame; MMW_ARGMAX_DENSE_MIN)
-    // and the plane has a kernel (128 chirps); covers the first dense_cap entries of the list, the direct kernels the rest.
-    const int max_cells = C == 128 ? cells64_max_cells(S, C) : 0;
+    // and the plane has a kernel (cells64_plan: 128 chirps, or a chirp count of k_cells64_mixed with MMW_ARGMAX_DENSE_MIXED on);
+    // covers the first dense_cap entries of the list, the direct kernels the rest.
+    Cells64Plan plan = cells64_plan(S, C);
+    if (plan.kind == C64_KIND_MIXED && !opt_int(ctx, "MMW_ARGMAX_DENSE_MIXED", ARGMAX_DENSE_MIXED_DEFAULT)) plan = Cells64Plan{};
+    const int max_cells = plan.cells;
     const int dense_min = max_cells > 0 ? std::max(1, opt_int(ctx, "MMW_ARGMAX_DENSE_MIN", 8 * n_frames)) : 0;
     const int dense_cap = dense_min > 0 ? (int)std::min<long>(list_cap, 256L * n_frames) : 0;
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -2071,7 +2081,7 @@ int mmw_angle_argmax_exact(mmw_ctx *ctx, const void *d_cubes, const float *d_l1,
     ra.dense_min = dense_min;
     ra.dense_cap = dense_cap;
     if (dense_min > 0) {
-        MMW_TRY(launch_cells64(ctx, ra, d_counts, d_flagpos, dense_min, d_cells, n_frames, max_cells));
+        MMW_TRY(launch_cells64(ctx, ra, d_counts, d_flagpos, dense_min, d_cells, n_frames, plan));
         Argmax64ListArgs la{d_cells, d_nflag, d_list, dense_min, dense_cap, n_ant, A, shift, d_idx, ra.twA};
         hipLaunchKernelGGL(k_argmax64_list, dim3((unsigned)std::min(std::max(dense_cap / 4, 1), 4 * ctx->num_cu)), dim3(256), 0, ctx->stream, la);
         MMW_TRY(check_launch("argmax64_list"));
@@ -2626,8 +2636,8 @@ int mmw_angle_argmax_cells64(mmw_ctx *ctx, const void *d_cells, int32_t *d_idx, 
     return check_launch("argmax64_cells");
 }
 
-// The float64 range-Doppler cells behind the exact argmax, read out: the dense route is k_cells64<128> itself with every listed
-// detection marked flagged (list position f * cap + det, so its output array IS d_out), the direct route the slices of
+// The float64 range-Doppler cells behind the exact argmax, read out: the dense routes are k_cells64<128> and k_cells64_mixed<C>
+// themselves with every listed detection marked flagged (list position f * cap + det, so its output array IS d_out), the direct route the slices of
 // k_argmax_refine_part added in k_argmax_refine_finish's order.  A test entry: it synchronises and validates the list on the host.
 int mmw_rd_cells64_at(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_dets, const int32_t *d_counts, void *d_out, int n_frames,
                       int V, int S, int C, int cap, const int *h_ant, int n_ant, int route) {
@@ -2635,11 +2645,16 @@ int mmw_rd_cells64_at(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_dets, 
     MMW_JOIN(ctx);
     MMW_REQUIRE(n_frames >= 0 && n_frames <= 65535 && V > 0 && S > 0 && S <= 65535 && C > 0 && cap >= 0, "bad shape");
     MMW_REQUIRE((long)n_frames * cap < (1L << 31), "too many detection slots for one call");
-    MMW_REQUIRE(route == MMW_CELLS64_DENSE || route == MMW_CELLS64_DIRECT, "route must be MMW_CELLS64_DENSE or MMW_CELLS64_DIRECT");
+    MMW_REQUIRE(route == MMW_CELLS64_DENSE || route == MMW_CELLS64_DIRECT || route == MMW_CELLS64_DENSE_MIXED,
+                "route must be MMW_CELLS64_DENSE, MMW_CELLS64_DIRECT or MMW_CELLS64_DENSE_MIXED");
     AntList ants{};
     MMW_TRY(fill_ant_list(h_ant, n_ant, V, MAX_ANT, &ants));
-    const int max_cells = C == 128 ? cells64_max_cells(S, C) : 0;
-    if (route == MMW_CELLS64_DENSE && max_cells == 0)
+    // MMW_CELLS64_DENSE: the 128-chirp kernel only; MMW_CELLS64_DENSE_MIXED: k_cells64_mixed<C>, also at C == 128
+    Cells64Plan plan{};
+    if (route == MMW_CELLS64_DENSE && C == 128) plan = cells64_plan(S, C);
+    if (route == MMW_CELLS64_DENSE_MIXED) plan = cells64_mixed_plan(S, C);
+    const bool dense = route != MMW_CELLS64_DIRECT;
+    if (dense && plan.kind == C64_KIND_NONE)
         return set_error(MMW_ERR_UNSUPPORTED, "no dense float64 cell kernel for %d x %d planes", S, C);
     if (n_frames == 0 || cap == 0) return MMW_OK;
     const int list_cap = n_frames * cap;
@@ -2654,12 +2669,12 @@ int mmw_rd_cells64_at(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_dets, 
         for (int det = 0; det < std::min(std::max(counts[f], 0), cap); ++det) {
             const int slot = f * cap + det, r = dets[2 * (size_t)slot], d = dets[2 * (size_t)slot + 1];
             MMW_REQUIRE(r >= 0 && r < S && d >= 0 && d < C, "detection %d of frame %d lies outside the %d x %d plane", det, f, S, C);
-            if (route == MMW_CELLS64_DENSE) host[64 + slot] = slot + 1;
+            if (dense) host[64 + slot] = slot + 1;
             else host[64 + n] = slot;
             ++n;
         }
     if (n == 0) return MMW_OK;
-    host[0] = route == MMW_CELLS64_DENSE ? list_cap : n;
+    host[0] = dense ? list_cap : n;
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const int parts = refine_parts(n_frames);
     const size_t list_bytes = up(host.size() * sizeof(int));
@@ -2673,8 +2688,8 @@ int mmw_rd_cells64_at(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_dets, 
                              n_frames, V, S, C, cap, MAX_ANT));
     ra.ants = ants;
     int rc = MMW_OK;
-    if (route == MMW_CELLS64_DENSE) {
-        rc = launch_cells64(ctx, ra, d_counts, d_list, 1, (cplx<double> *)d_out, n_frames, max_cells);
+    if (dense) {
+        rc = launch_cells64(ctx, ra, d_counts, d_list, 1, (cplx<double> *)d_out, n_frames, plan);
     } else {
         MMW_TRY(launch_refine_part(ctx, ra, std::min(n, 512)));
         hipLaunchKernelGGL(k_refine_cells_sum, dim3((unsigned)(((long)n * n_ant + 255) / 256)), dim3(256), 0, ctx->stream, ra,
@@ -2730,6 +2745,23 @@ int mmw_diag_rd_plan(int S, int C, int float64, int plan[8]) {
         plan[6] = pl.c2;
         plan[7] = (int)pl.lds_bytes;
     }
+    return MMW_OK;
+}
+
+int mmw_diag_cells64_plan(int S, int C, int plan[8]) {
+    MMW_REQUIRE(plan && S > 0 && C > 0, "bad argument");
+    for (int i = 0; i < 8; ++i) plan[i] = 0;
+    const Cells64Plan p = cells64_plan(S, C);
+    plan[0] = p.kind;
+    if (p.kind != C64_KIND_NONE) {
+        plan[1] = p.R1;
+        plan[2] = p.R2;
+        plan[3] = p.rows;
+        plan[4] = (int)p.lds;
+        plan[5] = p.cells;
+        plan[6] = p.pitch;
+    }
+    plan[7] = cells64_mixed_plan(S, C).kind == C64_KIND_MIXED;
     return MMW_OK;
 }
 
