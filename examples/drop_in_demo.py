@@ -14,11 +14,12 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mmwave_radar_processing_amd import synth  # noqa: E402
-from mmwave_radar_processing_amd.batch import FramePipeline  # noqa: E402
+from mmwave_radar_processing_amd.batch import FramePipeline, micro_doppler_history  # noqa: E402
 from mmwave_radar_processing_amd.config_managers import ConfigManager  # noqa: E402
 from mmwave_radar_processing_amd.detectors import CaCFAR2D  # noqa: E402
-from mmwave_radar_processing_amd.processors import (PointCloudGenerator, RangeAngleProcessorDBSEnhanced,  # noqa: E402
-                                                    RangeDopplerProcessor, VirtualArrayReformatter)
+from mmwave_radar_processing_amd.processors import (MicroDopplerProcessor, PointCloudGenerator,  # noqa: E402
+                                                    RangeAngleProcessorDBSEnhanced, RangeDopplerProcessor,
+                                                    VirtualArrayReformatter)
 
 cm = ConfigManager()
 cm.load_cfg_text(synth.SYNTH_CFG_256x128x12)
@@ -39,9 +40,15 @@ print("point cloud", points.shape, "| detections", pcg.detector.dets.shape, "| t
 cube3d = RangeAngleProcessorDBSEnhanced(cm).compute_3d_windowed_fft(cube)
 print("angle-range-Doppler cube", cube3d.shape, cube3d.dtype)
 
+md = MicroDopplerProcessor(cm, target_ranges=[0, 1.0], num_frames_history=20)
+spectrogram = md.process(adc_cube=cube, **params)               # one more column per frame, newest first
+print("micro-Doppler spectrogram", spectrogram.shape, "| window rows", md.rows, "| newest column peak", spectrogram[:, 0].max())
+
 # batch: 64 frames generated in HBM, detections + point clouds for all of them in one pass
 pipe = FramePipeline(cm, max_frames=64, shape=(12, 256, 128), cfar=CaCFAR2D((4, 4), (2, 2), 1e-5),
                      az_antenna_idxs=range(8), el_antenna_idxs=[8, 9, 10, 11])
 pipe.synth(64, seed0=2024)
 clouds = pipe.point_clouds()
 print("batch:", len(clouds), "frames,", sum(c.shape[0] for c in clouds), "points")
+rows = pipe.micro_doppler(target_ranges=(0, 1.0), rx_idx=0)    # the column every frame adds to the spectrogram, in one launch
+print("batch micro-Doppler rows", rows.shape, "| spectrogram after the batch", micro_doppler_history(rows, 20).shape)

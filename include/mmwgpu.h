@@ -175,6 +175,17 @@ int mmw_dbs_gather(mmw_ctx *ctx, const float *d_mag, const int *h_ang_idx, const
  *   Profile family "dbs_sharpen" (the range-Doppler pass counts under "rd"). */
 int mmw_dbs_sharpen(mmw_ctx *ctx, const void *d_cubes, void *d_rd, const int32_t *h_ang_idx, const int32_t *h_vel_idx,
                     float *d_out, int n_frames, int V, int S, int C, int A, const int *h_rx, int n_rx, int n_out);
+/* mmw_micro_doppler: d_out[F][C] float32 = the micro-Doppler row of every frame,
+ *     d_out[f][c] = max_{row_lo <= r <= row_hi} | X_f[r][(c + C - C/2) mod C] |,   X_f = FFT_S FFT_C( d_cubes[f][rx_idx] ),
+ *   no window, np.fft.fftshift's convention on the chirp axis (odd C included).  This is the column that
+ *   MicroDopplerProcessor.process (processors/micro_doppler_resp.py:91-114) rolls into its spectrogram: |fftshift(fft2(x[rx]))|,
+ *   the rows of the range window, np.max over them.  Only antenna rx_idx's [S][C] slab of a frame is read, only the rows of the
+ *   window are computed (a partial DFT over fast time, direct DFTs over slow time, float32), and nothing but the C floats of a
+ *   frame is written.  Any S, C >= 1 up to 3400 chirps (MMW_ERR_UNSUPPORTED beyond: the rows in flight live in the LDS).
+ *   MMW_ERR_INVALID (nothing launched, d_out untouched): a null pointer, n_frames < 0, rx_idx outside [0, V), row_lo > row_hi,
+ *   a row outside [0, S).  n_frames == 0: MMW_OK, nothing launched.  Profile family "micro_doppler". */
+int mmw_micro_doppler(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C, int rx_idx, int row_lo,
+                      int row_hi);
 /* mmw_mean_over_range: d_out[F][C][A] float32 = mean over range rows [s_lo, s_hi) of d_mag[F][A][S][C];
  *   with mmw_chain3d(flags | MAGNITUDE) this is DopplerAzimuthProcessor.process, coarse path
  *   (processors/doppler_azimuth_resp.py:84-128,296-334,419-491): range FFT -> range-window mask ->

@@ -75,6 +75,7 @@ _SIGNATURES = {
     "mmw_chain3d_raw_i16": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
     "mmw_dbs_gather": [_vp, _vp, _ip, _ip, _vp, _i, _i, _i, _i, _i],
     "mmw_dbs_sharpen": [_vp, _vp, _vp, _ip, _ip, _vp, _i, _i, _i, _i, _i, _ip, _i, _i],
+    "mmw_micro_doppler": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
     "mmw_mean_over_range": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i],
     "mmw_doppler_azimuth": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i],
     "mmw_doppler_azimuth_zoom": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_d), _i, _i],

@@ -162,6 +162,21 @@ def dbs_branches(dbs, velocities_ned: np.ndarray) -> np.ndarray:
     return sharp
 
 
+def micro_doppler_history(rows: np.ndarray, num_frames_history: int) -> np.ndarray:
+    """The ``(C, H)`` spectrogram a ``MicroDopplerProcessor(num_frames_history=H)`` holds after stepping, from a reset, through the
+    frames whose rows are ``rows`` (``[n, C]``, oldest first -- ``FramePipeline.micro_doppler``'s output, or the concatenation of
+    it over ``stream()`` chunks): the newest row in column 0, zeros behind the frames seen."""
+    rows = np.asarray(rows, dtype=np.float64)
+    H = int(num_frames_history)
+    if rows.ndim != 2 or H < 0:
+        raise ValueError(f"micro_doppler_history: rows must be [n_frames, C] and num_frames_history >= 0, got {rows.shape}, {H}")
+    out = np.zeros((rows.shape[1], H))
+    kept = min(H, rows.shape[0])
+    if kept:
+        out[:, :kept] = rows[::-1][:kept].T
+    return out
+
+
 def _runs(flags: np.ndarray):
     """(start, stop, value) of every run of equal consecutive entries of a bool array."""
     f0 = 0
@@ -462,6 +477,32 @@ class FramePipeline:
         frames below ``dbs.min_vel_dbs`` are NOT written (``self.dbs_sharpened`` says which frames they are)."""
         self._dbs_launch(dbs, velocities_ned, rx_antennas, chirp_idx, with_slow=False)
         return self.d_dbs
+
+    def micro_doppler_device(self, target_ranges=(0, 1.0), rx_idx: int = 0) -> _lib.DeviceBuffer:
+        """The micro-Doppler rows of ``micro_doppler`` left in HBM: float32 ``[n_frames][C]``, nothing downloaded."""
+        from .processors.micro_doppler_resp import window_rows
+        # every argument check comes before the first use of self.ctx / self.bufs
+        _, lo, hi = window_rows(self.range_bins, target_ranges)
+        if len(self.range_bins) != self.S or len(self.vel_bins) != self.C:
+            raise ValueError(f"micro_doppler: cubes of {self.S} samples x {self.C} chirps do not match the configuration's "
+                             f"{len(self.range_bins)} range bins x {len(self.vel_bins)} velocity bins")
+        rx = int(rx_idx)
+        if not -self.V <= rx < self.V:
+            raise IndexError(f"micro_doppler: rx_idx {rx_idx} is out of bounds for {self.V} antennas")
+        self.d_micro = self.bufs.get("micro_doppler", max(self.n_frames, 1) * self.C * 4)
+        _lib.check(self.ctx.lib.mmw_micro_doppler(self.ctx.handle, self.d_in.ptr, self.d_micro.ptr, self.n_frames, self.V, self.S,
+                                                  self.C, rx % self.V, lo, hi))
+        return self.d_micro
+
+    def micro_doppler(self, target_ranges=(0, 1.0), rx_idx: int = 0) -> np.ndarray:
+        """Row f of the float64 ``[n_frames, C]`` result is what ``MicroDopplerProcessor(cm, target_ranges).process(cube_f, rx_idx)``
+        puts into column 0 of its spectrogram (reference: processors/micro_doppler_resp.py:91-114, stepped per frame by every
+        movie and viewer loop): ``max`` over the range rows of the window of ``|fftshift_C(fft2(cube_f[rx_idx]))|``, from one
+        ``mmw_micro_doppler`` call on the resident cubes.  The rows do not depend on each other: ``micro_doppler_history(rows,
+        H)`` is the processor's buffer after these frames.  Works on whatever ``load`` / ``load_raw`` / ``load_raw_i16`` /
+        ``synth`` / a ``stream()`` chunk left resident; ``cfar=``, ``ground=`` and ``sequential=`` play no part."""
+        d = self.micro_doppler_device(target_ranges, rx_idx)
+        return d.download((self.n_frames, self.C), np.float32).astype(np.float64)
 
     def _alloc_detect(self):
         F, V, cap = self.n_frames, self.V, self.cap
@@ -972,6 +1013,12 @@ class MultiDeviceFramePipeline:
             raise RuntimeError(f"joined {len(counts)} per-frame fits for {self.n_frames} frames")
         self.n_ego_flagged = sum(getattr(self.parts[r], "n_ego_flagged", 0) for r in live)
         return ego_state_scan(estimator, fits, counts)
+
+    def micro_doppler(self, target_ranges=(0, 1.0), rx_idx: int = 0) -> np.ndarray:
+        """``FramePipeline.micro_doppler`` of every shard, concatenated in frame order (the rows are independent of each other;
+        ``micro_doppler_history`` of the result is the spectrogram)."""
+        rows = self._join(self._each(lambda r: self.parts[r].micro_doppler(target_ranges, rx_idx)))
+        return np.asarray(rows, dtype=np.float64).reshape(self.n_frames, self.shape[2])
 
     def chain3d(self, magnitude: bool = False, out: Optional[np.ndarray] = None) -> Optional[np.ndarray]:
         """3-D windowed FFT of every frame on its device.  ``out`` (optional, caller-owned ``[F, A, S, C]`` complex64 /
