@@ -186,6 +186,25 @@ int mmw_dbs_sharpen(mmw_ctx *ctx, const void *d_cubes, void *d_rd, const int32_t
  *   a row outside [0, S).  n_frames == 0: MMW_OK, nothing launched.  Profile family "micro_doppler". */
 int mmw_micro_doppler(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C, int rx_idx, int row_lo,
                       int row_hi);
+/* mmw_synth_array: the synthetic-array images of n_out frames of a resident batch, their windows read in place,
+ *     d_out[i] = FFT_S( hann(S) . ( X_i[S][E] x W_i[E][T] ) ),   W_i[e][t] = hamming(E)[e] exp(j 2 pi d_t . p_{i,e} / lambda),
+ *   Cv = ceil(C / k), E = H Cv, element e = (h, j) of X_i = d_cubes[h_frames[i] - H + 1 + h][v][s][j k]: the last H frames of
+ *   every k-th chirp of virtual antenna v, oldest frame first -- SyntheticArrayBeamformerProcessor's history_acd_cube_valid_chirps
+ *   (processors/simple_synthetic_array_beamformer_processor_multiFrame.py:818-872) without the [n_out][S][E] copy: this is
+ *   mmw_bartlett with its operand gathered from d_cubes [n_resident][V][S][C] c64 inside the kernels.  A window frame with a
+ *   negative index is all zeros and is never read; the Hamming taper and the geometry still count its elements.
+ *   h_frames [n_out] host int32, strictly ascending, each in [0, n_resident); h_P [n_out][3][E] host float64 (element positions
+ *   of every window); h_dirs [3][T] host float64; d_out [n_out][S][T] c64.  The host arrays are free again when the call returns.
+ *   MMW_ERR_INVALID (nothing enqueued, d_out untouched): a null pointer, v outside [0, V), k < 1, H < 1, T < 1, lambda_m <= 0,
+ *   n_out outside [0, 65535], h_frames unsorted / repeated / out of range.  n_out == 0: MMW_OK, nothing launched.
+ *   The MMW_BARTLETT_* options select the kernels as they do for mmw_bartlett.  Profile family "synth_array".
+ * mmw_diag_synth_array_window: the window arithmetic behind it, host only (no device, no context): the run of n elements from e0
+ *   of output frame `frame` cut at the frame boundaries -- h_segs[4 i ..] = (window slot, resident frame or negative, first chirp
+ *   index j, elements) for up to cap segments; info[0] = segments, [1] = first resident frame read (-1: none), [2] = the run may be
+ *   read with 16-byte loads, [3] = the tile kernels' 16-byte path is legal for runs of n at this (C, k, H). */
+int mmw_synth_array(mmw_ctx *ctx, const void *d_cubes, int n_resident, int V, int S, int C, int v, int k, int H,
+                    const int32_t *h_frames, int n_out, const double *h_P, const double *h_dirs, int T, double lambda_m, void *d_out);
+int mmw_diag_synth_array_window(int C, int k, int H, int frame, int e0, int n, int32_t *h_segs, int cap, int32_t info[4]);
 /* mmw_mean_over_range: d_out[F][C][A] float32 = mean over range rows [s_lo, s_hi) of d_mag[F][A][S][C];
  *   with mmw_chain3d(flags | MAGNITUDE) this is DopplerAzimuthProcessor.process, coarse path
  *   (processors/doppler_azimuth_resp.py:84-128,296-334,419-491): range FFT -> range-window mask ->

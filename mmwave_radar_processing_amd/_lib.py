@@ -76,6 +76,8 @@ _SIGNATURES = {
     "mmw_dbs_gather": [_vp, _vp, _ip, _ip, _vp, _i, _i, _i, _i, _i],
     "mmw_dbs_sharpen": [_vp, _vp, _vp, _ip, _ip, _vp, _i, _i, _i, _i, _i, _ip, _i, _i],
     "mmw_micro_doppler": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
+    "mmw_synth_array": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ip, _i, C.POINTER(_d), C.POINTER(_d), _i, _d, _vp],
+    "mmw_diag_synth_array_window": [_i, _i, _i, _i, _i, _i, _ip, _i, _ip],
     "mmw_mean_over_range": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i],
     "mmw_doppler_azimuth": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i],
     "mmw_doppler_azimuth_zoom": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_d), _i, _i],

@@ -8,6 +8,7 @@ the host-side join of per-frame results (``gather_frames``) touches ``torch.dist
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -175,6 +176,30 @@ def micro_doppler_history(rows: np.ndarray, num_frames_history: int) -> np.ndarr
     if kept:
         out[:, :kept] = rows[::-1][:kept].T
     return out
+
+
+def synthetic_array_geometry(proc, velocities) -> Tuple[np.ndarray, np.ndarray]:
+    """``(valid, P)``: what a freshly configured ``SyntheticArrayBeamformerProcessor`` like ``proc`` would hold in
+    ``array_geometry_valid`` / ``array_geometry`` after each of the frames whose velocities are ``velocities [n, 3]`` -- ``valid``
+    bool ``[n]``, ``P`` float64 ``[n_valid, 3, E]`` (``E = num_frames * Cv``, oldest frame of the window first: the layout
+    ``mmw_synth_array`` and ``SyntheticArrayBeamformerCore.contract`` take).  The history before frame 0 is zero velocity.
+    ``proc`` is only read, never stepped."""
+    from .processors.synthetic_array_beamformer import gate, window_geometry
+    vel = np.asarray(velocities, dtype=np.float64)
+    if vel.ndim != 2 or vel.shape[1] != 3:
+        raise ValueError(f"synthetic_array_geometry: velocities must be [n_frames, 3], got {vel.shape}")
+    H, n = int(proc.num_frames), len(vel)
+    padded = np.concatenate([np.zeros((H - 1, 3)), vel])
+    valid = np.zeros(n, dtype=bool)
+    geoms = []
+    for f in range(n):
+        hist = padded[f:f + H]
+        valid[f] = gate(hist, proc.min_vel, proc.max_vel, proc.max_vel_stdev)
+        if valid[f]:
+            g = window_geometry(hist, proc.chirp_start_times_us, proc.frame_period_ms)
+            geoms.append(g.transpose(1, 0, 2).reshape(3, -1))
+    E = H * len(proc.chirp_start_times_us)
+    return valid, (np.stack(geoms) if geoms else np.zeros((0, 3, E)))
 
 
 def _runs(flags: np.ndarray):
@@ -503,6 +528,53 @@ class FramePipeline:
         ``synth`` / a ``stream()`` chunk left resident; ``cfar=``, ``ground=`` and ``sequential=`` play no part."""
         d = self.micro_doppler_device(target_ranges, rx_idx)
         return d.download((self.n_frames, self.C), np.float32).astype(np.float64)
+
+    def synthetic_array_device(self, proc, velocities) -> Tuple[np.ndarray, _lib.DeviceBuffer]:
+        """``(frames, buffer)``: the images of ``synthetic_array`` left in HBM, complex64 ``[n_valid][S][n_az * n_el]``, nothing
+        downloaded."""
+        # every argument check comes before the first use of self.ctx / self.bufs
+        if getattr(proc, "enable_calibration", False):
+            raise ValueError("synthetic_array: array calibration is not part of this build")
+        cm = proc.config_manager
+        num_tx = int(cm.frameCfg_end_index) - int(cm.frameCfg_start_index) + 1
+        if self.V % num_tx or self.S != proc.num_range_bins or self.C * num_tx != proc.chirps_per_frame:
+            raise ValueError(f"synthetic_array: cubes [{self.V}, {self.S}, {self.C}] do not match the processor's configuration "
+                             f"({num_tx} transmitters, {proc.num_range_bins} samples, {proc.chirps_per_frame} chirps per frame)")
+        num_rx = self.V // num_tx
+        rx, tx = int(proc.receiver_idx), int(proc.chirp_cfg_idx) - int(cm.frameCfg_start_index)
+        if not (0 <= rx < num_rx and 0 <= tx < num_tx):
+            raise ValueError(f"synthetic_array: receiver {rx} / chirp configuration {proc.chirp_cfg_idx} is not one of {num_rx} "
+                             f"receivers x {num_tx} transmitters")
+        vel = np.asarray(velocities, dtype=np.float64)
+        if vel.shape != (self.n_frames, 3):
+            raise ValueError(f"synthetic_array: velocities must be [{self.n_frames}, 3] (one row per resident frame), got {vel.shape}")
+        valid, P = synthetic_array_geometry(proc, vel)
+        frames = np.flatnonzero(valid).astype(np.int32)
+        dirs = np.ascontiguousarray(np.asarray(proc.d, dtype=np.float64).reshape(3, -1))
+        T, H, k = dirs.shape[1], int(proc.num_frames), int(proc.stride)
+        P = np.ascontiguousarray(P)
+        self.d_synth = self.bufs.get("synth_array", max(len(frames), 1) * self.S * T * 8)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(self.ctx.lib.mmw_synth_array(self.ctx.handle, self.d_in.ptr, self.n_frames, self.V, self.S, self.C, tx * num_rx + rx,
+                                                k, H, frames.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(frames),
+                                                P.ctypes.data_as(dp), dirs.ctypes.data_as(dp), T, float(proc.lambda_m),
+                                                self.d_synth.ptr))
+        return frames.astype(np.int64), self.d_synth
+
+    def synthetic_array(self, proc, velocities) -> Tuple[np.ndarray, np.ndarray]:
+        """``(frames, responses)``: ``responses[i]`` (complex128 ``[n_valid, S, n_az, n_el]``) is what a fresh
+        ``SyntheticArrayBeamformerProcessor`` configured like ``proc`` returns for resident frame ``frames[i]`` when it is stepped
+        through the resident frames with ``velocities [n_frames, 3]``; ``frames`` are the frames whose geometry is valid (the
+        others return ``np.empty(0)`` there).  One ``mmw_synth_array`` call: the window of every valid frame (``num_frames``
+        frames of every ``stride``-th chirp of virtual antenna ``chirp_cfg_idx * num_rx + receiver_idx``) is read in place from
+        the resident cubes, the geometry table comes from ``synthetic_array_geometry``.  ``proc`` is not touched.  Works on
+        whatever ``load`` / ``load_raw`` / ``load_raw_i16`` / ``synth`` left resident.
+        Out of scope: carrying the ``num_frames - 1`` frames of history across ``stream()`` chunks or calls (every call starts
+        from a reset history), and ``MultiDeviceFramePipeline`` (a shard needs a halo of ``num_frames - 1`` frames)."""
+        frames, d = self.synthetic_array_device(proc, velocities)
+        n_az, n_el = np.shape(proc.d)[1:]
+        out = d.download((len(frames), self.S, n_az * n_el), np.complex64) if len(frames) else np.zeros((0, self.S, n_az * n_el), np.complex64)
+        return frames, out.astype(np.complex128).reshape(len(frames), self.S, n_az, n_el)
 
     def _alloc_detect(self):
         F, V, cap = self.n_frames, self.V, self.cap

@@ -17,6 +17,7 @@
 namespace mmw {
 
 typedef double v4d __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // LDS traffic inside one wave needs no hardware barrier (DS instructions of a wave execute in order); the compiler
 // must not move accesses across the hand-over
@@ -34,9 +35,40 @@ __device__ __forceinline__ cplx<float> and_mask(cplx<float> v, bool keep) {
     return cplx<float>{__builtin_bit_cast(float, __builtin_bit_cast(unsigned, re) & m), __builtin_bit_cast(float, __builtin_bit_cast(unsigned, im) & m)};
 }
 
+// Where the A operand of the contractions below lives: a policy object passed to the kernels by value.
+//   row(A, b, m, sa, lda)      handle of row m of batch b (batch stride sa, row pitch lda); row_packed(A, b, m, M, K): the same
+//                              for [b][M][K] without padding
+//   run<N>(row, k0, K, out)    elements k0 .. k0 + N - 1 of the row, indices clamped to K - 1; returns a mask whose bit j says that
+//                              out[j] is an element of the operand (a clear bit: the element is zero by definition and the value
+//                              loaded in its place must be masked away)
+//   run16<N>(row, k0, out)     the same N elements (N even) as 16-byte loads, legal only where fast(E, N) said so
+//   fast(E, n)                 host: every chunk whole and every run of n elements, starting at a multiple of n, contiguous and
+//                              16-byte aligned
+// ARows is the contiguous [b][M][K] array mmw_bartlett is given: an empty object whose methods are the index expressions the
+// kernels had before the policy existed.  mmw_synth_array.h has the second policy (rows gathered from a window of resident frames).
+struct ARows {
+    static constexpr bool windowed = false;
+    struct Row {
+        const cplx<float> *p;
+    };
+    __device__ __forceinline__ Row row(const cplx<float> *A, long b, int m, long sa, int lda) const { return Row{A + b * sa + (long)m * lda}; }
+    __device__ __forceinline__ Row row_packed(const cplx<float> *A, long b, int m, int M, int K) const { return Row{A + (b * M + m) * (long)K}; }
+    template <int N> __device__ __forceinline__ unsigned run(const Row &r, int k0, int K, cplx<float> (&out)[N]) const {
+#pragma unroll
+        for (int j = 0; j < N; ++j) out[j] = r.p[k0 + j < K ? k0 + j : K - 1];
+        return ~0u;
+    }
+    template <int N> __device__ __forceinline__ void run16(const Row &r, int k0, f32x4 (&out)[N / 2]) const {
+        const f32x4 *src = reinterpret_cast<const f32x4 *>(r.p + k0);
+#pragma unroll
+        for (int j = 0; j < N / 2; ++j) out[j] = src[j];
+    }
+    bool fast(int E, int) const { return (E & 31) == 0; }
+};
+
 // W[f][e][t] (complex64, row-major [E][Tp] per frame); phase reduced mod 1 turn in float64 before the sincos.
 // P [F][3][E] element positions of each frame's (synthetic) array, dirs [3][T] steering directions.
-__global__ __launch_bounds__(256) void k_steer(cplx<float> *W, const double *P, const double *dirs,
+static __global__ __launch_bounds__(256) void k_steer(cplx<float> *W, const double *P, const double *dirs,
                                                 const float *hamming, int E, int T, int Tp, double inv_lambda) {
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
     if (gid >= (long)E * Tp) return;
@@ -64,13 +96,13 @@ constexpr int CG_LDS_FLOATS = 2 * CG_TK * CG_PA + 2 * CG_TK * CG_PB;       // on
 // ksplit > 1 (small batches: a 256 x 64 x 256 product is two workgroups stepping through K one latency at a time):
 // blockIdx.z = batch * ksplit + kz, workgroup kz multiplies the K range [kz kc, (kz + 1) kc) and writes its partial
 // product to Cm + kz * spart; k_sum_parts adds the partials in a fixed order.
+template <class AP>
 __global__ __launch_bounds__(256) void k_cgemm_mfma(const cplx<float> *__restrict__ A, const cplx<float> *__restrict__ B,
                                                      cplx<float> *__restrict__ Cm, int M, int N, int K, int lda,
-                                                     int ldb, int ldc, long sa, long sb, long sc, int ksplit, int kc, long spart) {
+                                                     int ldb, int ldc, long sa, long sb, long sc, int ksplit, int kc, long spart, AP ap) {
     __shared__ float lds[2 * CG_LDS_FLOATS];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int bz = blockIdx.z / ksplit, kz = blockIdx.z - bz * ksplit;
-    A += (long)bz * sa;
     B += (long)bz * sb;
     Cm += (long)bz * sc + (long)kz * spart;
     const int k_begin = kz * kc;
@@ -80,16 +112,15 @@ __global__ __launch_bounds__(256) void k_cgemm_mfma(const cplx<float> *__restric
     // global -> register staging: A rows (thread = row, 8 consecutive k), B rows (thread = k, 4 consecutive n)
     const int a_row = t >> 1, a_k = (t & 1) * 8, b_k = t >> 4, b_n = (t & 15) * 4;
     cplx<float> ra[8], rb[4];
+    const typename AP::Row arow = ap.row(A, bz, m0 + a_row < M ? m0 + a_row : M - 1, sa, lda);
     auto fetch = [&](int k0) {
         // unconditional, clamped loads + a select afterwards: a load under a condition is followed by its own s_waitcnt, and the
         // twelve loads of a step then cost twelve trips to memory one after the other (this was 5 k of a step's 7 k clocks)
-        const int gm = m0 + a_row, gmc = gm < M ? gm : M - 1;
+        const int gm = m0 + a_row;
+        cplx<float> av[8];
+        const unsigned live = ap.template run<8>(arow, k0 + a_k, K, av);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int gk = k0 + a_k + j;
-            const cplx<float> v = A[(long)gmc * lda + (gk < K ? gk : K - 1)];
-            ra[j] = and_mask(v, (gm < M) & (gk < K));
-        }
+        for (int j = 0; j < 8; ++j) ra[j] = and_mask(av[j], (gm < M) & (k0 + a_k + j < K) & (bool)((live >> j) & 1u));
         const int gk = k0 + b_k, gkc = gk < K ? gk : K - 1;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -172,14 +203,14 @@ __device__ __forceinline__ void split_bf16x3_4(const float (&v)[4], unsigned (&p
         p3[q] = (__builtin_bit_cast(unsigned, sa) >> 16) | (__builtin_bit_cast(unsigned, sb) & 0xffff0000u);
     }
 }
+template <class AP>
 __global__ __launch_bounds__(256, 2) void k_cgemm_bf16x3(const cplx<float> *__restrict__ A, const cplx<float> *__restrict__ B,
                                                        cplx<float> *__restrict__ Cm, int M, int N, int K, int lda,
-                                                       int ldb, int ldc, long sa, long sb, long sc, int ksplit, int kc, long spart) {
+                                                       int ldb, int ldc, long sa, long sb, long sc, int ksplit, int kc, long spart, AP ap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned short *lds = reinterpret_cast<unsigned short *>(smem);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int bz = blockIdx.z / ksplit, kz = blockIdx.z - bz * ksplit;
-    A += (long)bz * sa;
     B += (long)bz * sb;
     Cm += (long)bz * sc + (long)kz * spart;
     const int k_begin = kz * kc;
@@ -189,15 +220,12 @@ __global__ __launch_bounds__(256, 2) void k_cgemm_bf16x3(const cplx<float> *__re
     // global -> registers: A rows (thread = row, 8 consecutive k), B columns (thread = column, 4 consecutive k)
     const int a_row = t >> 1, a_k = (t & 1) * 8, b_n = t & 63, b_k = (t >> 6) * 4;
     cplx<float> ra[8], rb[4];
+    const typename AP::Row arow = ap.row(A, bz, m0 + a_row < M ? m0 + a_row : M - 1, sa, lda);
+    unsigned a_live = ~0u;                              // which of ra[] are elements of the operand (ARows: all, folded away)
     auto fetch = [&](int k0) {
         // unconditional, clamped loads + a select afterwards: a load under a condition is followed by its own s_waitcnt, and the
         // twelve loads of a step then cost twelve trips to memory one after the other (this was 5 k of a step's 7 k clocks)
-        const int gm = m0 + a_row, gmc = gm < M ? gm : M - 1;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int gk = k0 + a_k + j;
-            ra[j] = A[(long)gmc * lda + (gk < K ? gk : K - 1)];           // (masked in stash(): the AND would wait for the load here)
-        }
+        a_live = ap.template run<8>(arow, k0 + a_k, K, ra);     // (masked in stash(): the AND would wait for the load here)
         const int gn = n0 + b_n, gnc = gn < N ? gn : N - 1;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -212,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void k_cgemm_bf16x3(const cplx<float> *__re
         const bool row_ok = m0 + a_row < M, col_ok = n0 + b_n < N;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const cplx<float> v = and_mask(ra[j], row_ok & (k0 + a_k + j < K));
+            const cplx<float> v = and_mask(ra[j], row_ok & (k0 + a_k + j < K) & (bool)((a_live >> j) & 1u));
             xr[j] = v.x;
             xi[j] = v.y;
         }
@@ -293,7 +321,7 @@ __global__ __launch_bounds__(256, 2) void k_cgemm_bf16x3(const cplx<float> *__re
         }
 }
 
-__global__ __launch_bounds__(256) void k_sum_parts(const cplx<float> *__restrict__ parts, cplx<float> *__restrict__ out, long n,
+static __global__ __launch_bounds__(256) void k_sum_parts(const cplx<float> *__restrict__ parts, cplx<float> *__restrict__ out, long n,
                                                     int ksplit) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -342,11 +370,11 @@ constexpr int BT_STRIP = 3 * 64 * 8 + 64 * 4;          // wave-private LDS: elem
 // vector float32 rates are the same 256 flop/clk/CU, evidently the same multipliers): every vector instruction in this
 // loop is paid in full, so the steering is trimmed to the minimum (float64 dot product + fract, one convert, two
 // transcendentals, two multiplies per element) and eight waves per workgroup (two per SIMD) only hide latencies.
-template <int NW, int NS, bool FAST, int VAR>
+template <int NW, int NS, bool FAST, int VAR, class AP>
 __global__ __launch_bounds__(64 * NW) void k_bartlett_tile(const cplx<float> *__restrict__ X, const double *__restrict__ P,
                                                             const double *__restrict__ dirs, const float *__restrict__ hamming,
                                                             cplx<float> *__restrict__ Cm, int S, int E, int T, int tiles_s, int NT,
-                                                            int MT, double inv_lambda, long long *clk) {
+                                                            int MT, double inv_lambda, long long *clk, AP ap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int CH = 2 * NS;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, ij = lane & 31;
@@ -366,7 +394,7 @@ __global__ __launch_bounds__(64 * NW) void k_bartlett_tile(const cplx<float> *__
     const int tc = n0 + ij < T ? n0 + ij : T - 1;
     const double dx = dirs[tc] * inv_lambda, dy = dirs[T + tc] * inv_lambda, dz = dirs[2 * T + tc] * inv_lambda;
     const int gm = m0 + ij < S ? m0 + ij : S - 1;
-    const cplx<float> *xrow = X + (f * S + gm) * (long)E;
+    const typename AP::Row xrow = ap.row_packed(X, f, gm, S, E);
     const double *Pf = P + f * 3 * E;
     // four accumulators: no MFMA waits for the result of the one issued just before it (summed after the loop)
     v16f acc_r = {0}, acc_i = {0}, acc_r2 = {0}, acc_i2 = {0};
@@ -381,14 +409,14 @@ __global__ __launch_bounds__(64 * NW) void k_bartlett_tile(const cplx<float> *__
         const float hv = (st_on && k0 + lane < E) ? hamming[e_st] : 0.f;
         f32x4 ra[NS / 2];
         if (FAST) {
-            const f32x4 *src = reinterpret_cast<const f32x4 *>(xrow + kb);
-#pragma unroll
-            for (int j = 0; j < NS / 2; ++j) ra[j] = src[j];
+            ap.template run16<NS>(xrow, kb, ra);
         } else {                                        // last chunk / odd row pitch: clamped 8-byte loads, taper 0 beyond E
+            cplx<float> av[NS];
+            const unsigned live = ap.template run<NS>(xrow, kb, E, av);
 #pragma unroll
             for (int j = 0; j < NS / 2; ++j) {
-                const int ka = kb + 2 * j < E ? kb + 2 * j : E - 1, kc = kb + 2 * j + 1 < E ? kb + 2 * j + 1 : E - 1;
-                const cplx<float> a = xrow[ka], c = xrow[kc];
+                const cplx<float> a = AP::windowed ? and_mask(av[2 * j], (live >> (2 * j)) & 1u) : av[2 * j];
+                const cplx<float> c = AP::windowed ? and_mask(av[2 * j + 1], (live >> (2 * j + 1)) & 1u) : av[2 * j + 1];
                 ra[j] = f32x4{a.x, a.y, c.x, c.y};
             }
         }
@@ -497,11 +525,11 @@ __global__ __launch_bounds__(64 * NW) void k_bartlett_tile(const cplx<float> *__
 // same kernel on 16 x 16 tiles (v_mfma_f32_16x16x32_bf16, the bfloat16 x 3 form only) spreads the frame over 64 workgroups
 // whose waves steer 8 values of k each (group g = lane >> 4 feeds k0 + 8 g + j) and issue 24 MFMAs of 16 cycles: the chain
 // per workgroup is half as long.  Used while the 32 x 32 tiling would leave three quarters of the chip without a workgroup.
-template <int NW, bool FAST>
+template <int NW, bool FAST, class AP>
 __global__ __launch_bounds__(64 * NW) void k_bartlett_tile16(const cplx<float> *__restrict__ X, const double *__restrict__ P,
                                                               const double *__restrict__ dirs, const float *__restrict__ hamming,
                                                               cplx<float> *__restrict__ Cm, int S, int E, int T, int tiles_s, int NT,
-                                                              int MT, double inv_lambda) {
+                                                              int MT, double inv_lambda, AP ap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int CH = 32;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, i16 = lane & 15;
@@ -517,7 +545,7 @@ __global__ __launch_bounds__(64 * NW) void k_bartlett_tile16(const cplx<float> *
     const int tc = n0 + i16 < T ? n0 + i16 : T - 1;
     const double dx = dirs[tc] * inv_lambda, dy = dirs[T + tc] * inv_lambda, dz = dirs[2 * T + tc] * inv_lambda;
     const int gm = m0 + i16 < S ? m0 + i16 : S - 1;
-    const cplx<float> *xrow = X + (f * S + gm) * (long)E;
+    const typename AP::Row xrow = ap.row_packed(X, f, gm, S, E);
     const double *Pf = P + f * 3 * E;
     v4f acc_r = {0}, acc_i = {0}, acc_r2 = {0}, acc_i2 = {0};
     const int n_chunks = (E + CH - 1) / CH;
@@ -529,14 +557,14 @@ __global__ __launch_bounds__(64 * NW) void k_bartlett_tile16(const cplx<float> *
         const float hv = (st_on && k0 + lane < E) ? hamming[e_st] : 0.f;
         f32x4 ra[4];
         if (FAST) {
-            const f32x4 *src = reinterpret_cast<const f32x4 *>(xrow + kb);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ra[j] = src[j];
+            ap.template run16<8>(xrow, kb, ra);
         } else {                                        // last chunk / odd row pitch: clamped 8-byte loads, taper 0 beyond E
+            cplx<float> av[8];
+            const unsigned live = ap.template run<8>(xrow, kb, E, av);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int ka = kb + 2 * j < E ? kb + 2 * j : E - 1, kc = kb + 2 * j + 1 < E ? kb + 2 * j + 1 : E - 1;
-                const cplx<float> a = xrow[ka], c = xrow[kc];
+                const cplx<float> a = AP::windowed ? and_mask(av[2 * j], (live >> (2 * j)) & 1u) : av[2 * j];
+                const cplx<float> c = AP::windowed ? and_mask(av[2 * j + 1], (live >> (2 * j + 1)) & 1u) : av[2 * j + 1];
                 ra[j] = f32x4{a.x, a.y, c.x, c.y};
             }
         }
@@ -588,27 +616,45 @@ __global__ __launch_bounds__(64 * NW) void k_bartlett_tile16(const cplx<float> *
     }
 }
 
-// d_X [F][S][E] c64, d_P [F][3][E] f64, d_dirs [3][T] f64 -> d_out [F][S][T] c64
-inline int bartlett(mmw_ctx *ctx, const void *d_X, const double *d_P, const double *d_dirs, void *d_out, int n_frames, int S,
-                    int E, int T, double lambda_m) {
-    const int Tp = (T + 3) & ~3;
-    const size_t w_bytes = (size_t)n_frames * E * Tp * sizeof(cplx<float>), c_bytes = (size_t)n_frames * S * T * sizeof(cplx<float>);
+// the K split of the tiled path and the scratch the contraction needs (W, the product, the partial products)
+struct BartlettPlan {
+    int Tp, ksplit, kc;
+    size_t w_bytes, c_bytes, bytes;
+};
+inline BartlettPlan bartlett_plan(const mmw_ctx *ctx, int n_frames, int S, int E, int T) {
+    BartlettPlan p;
+    p.Tp = (T + 3) & ~3;
+    p.w_bytes = (size_t)n_frames * E * p.Tp * sizeof(cplx<float>);
+    p.c_bytes = (size_t)n_frames * S * T * sizeof(cplx<float>);
     // small batches: split K over workgroups until about half the chip is busy (each part at least two K steps)
     const long wgs = (long)((T + CG_TN - 1) / CG_TN) * ((S + CG_TM - 1) / CG_TM) * n_frames;
     int ksplit = 1;
     if (wgs * 2 <= ctx->num_cu && E >= 4 * CG_TK)
         ksplit = (int)std::min<long>(std::min<long>(16, E / (2 * CG_TK)), ctx->num_cu / (2 * wgs));
     if (ksplit < 2) ksplit = 1;
-    const int kc = ksplit > 1 ? ((E + ksplit - 1) / ksplit + CG_TK - 1) / CG_TK * CG_TK : E;
-    if (ksplit > 1) ksplit = (E + kc - 1) / kc;         // no empty part
-    MMW_TRY(ensure_scratch(ctx, w_bytes + c_bytes * (ksplit > 1 ? ksplit + 1 : 1)));
-    cplx<float> *W = (cplx<float> *)ctx->scratch;
-    cplx<float> *Cm = (cplx<float> *)((char *)ctx->scratch + w_bytes);
+    p.kc = ksplit > 1 ? ((E + ksplit - 1) / ksplit + CG_TK - 1) / CG_TK * CG_TK : E;
+    if (ksplit > 1) ksplit = (E + p.kc - 1) / p.kc;     // no empty part
+    p.ksplit = ksplit;
+    p.bytes = p.w_bytes + p.c_bytes * (ksplit > 1 ? ksplit + 1 : 1);
+    return p;
+}
+
+// d_A: operand A as the policy `ap` addresses it (ARows: d_X [F][S][E] c64), d_P [F][3][E] f64, d_dirs [3][T] f64 -> d_out
+// [F][S][T] c64.  The first `head` bytes of the scratch belong to the caller (who has made the scratch large enough for head +
+// bartlett_plan().bytes if anything in it must survive this call).
+template <class AP>
+int bartlett_on(mmw_ctx *ctx, AP ap, const char *family, const void *d_X, const double *d_P, const double *d_dirs, void *d_out,
+                int n_frames, int S, int E, int T, double lambda_m, size_t head) {
+    const BartlettPlan plan = bartlett_plan(ctx, n_frames, S, E, T);
+    const int Tp = plan.Tp, kc = plan.kc, ksplit = plan.ksplit;
+    MMW_TRY(ensure_scratch(ctx, head + plan.bytes));
+    cplx<float> *W = (cplx<float> *)((char *)ctx->scratch + head);
+    cplx<float> *Cm = (cplx<float> *)((char *)ctx->scratch + head + plan.w_bytes);
     cplx<float> *Cparts = Cm + (size_t)n_frames * S * T;
     const void *ham, *hann;
     MMW_TRY(get_table<float>(ctx, TAB_HAMMING, E, &ham));
     MMW_TRY(get_table<float>(ctx, TAB_HANN, S, &hann));
-    ProfScope ps(ctx, "bartlett");
+    ProfScope ps(ctx, family);
     // small contractions (at most four 32 x 32 tiles per CU): steering evaluated inside the tile kernel
     const int tiles_s = (S + 31) / 32, NT = (T + 31) / 32;
     const long MT = (long)n_frames * tiles_s;     // (< 2^31: n_frames <= 65535)
@@ -628,18 +674,19 @@ inline int bartlett(mmw_ctx *ctx, const void *d_X, const double *d_P, const doub
             const long MT16 = (long)n_frames * tiles16;
             const unsigned grid16 = (unsigned)(8 * NT16 * ((MT16 + 7) / 8));
             const size_t lds16 = (size_t)nw * BT_STRIP + (size_t)nw * 2 * 4 * 64 * 4;
-            auto k16 = (E & 31) == 0 ? k_bartlett_tile16<8, true> : k_bartlett_tile16<8, false>;
+            auto k16 = ap.fast(E, 8) ? k_bartlett_tile16<8, true, AP> : k_bartlett_tile16<8, false, AP>;
             hipLaunchKernelGGL(k16, dim3(grid16), dim3(64 * nw), lds16, ctx->stream, (const cplx<float> *)d_X, d_P, d_dirs,
-                               (const float *)ham, Cm, S, E, T, tiles16, NT16, (int)MT16, 1.0 / lambda_m);
+                               (const float *)ham, Cm, S, E, T, tiles16, NT16, (int)MT16, 1.0 / lambda_m, ap);
             MMW_TRY(check_launch("bartlett_tile16"));
         } else {
-        auto kern = bf3 ? k_bartlett_tile<8, 16, false, 3> : k_bartlett_tile<8, 16, false, 1>;
-        if ((E & 31) == 0) kern = poly ? k_bartlett_tile<8, 16, true, 0> : bf3 ? k_bartlett_tile<8, 16, true, 3> : k_bartlett_tile<8, 16, true, 1>;
-        else if (poly) kern = k_bartlett_tile<8, 16, false, 0>;
+        auto kern = bf3 ? k_bartlett_tile<8, 16, false, 3, AP> : k_bartlett_tile<8, 16, false, 1, AP>;
+        if (ap.fast(E, 16))
+            kern = poly ? k_bartlett_tile<8, 16, true, 0, AP> : bf3 ? k_bartlett_tile<8, 16, true, 3, AP> : k_bartlett_tile<8, 16, true, 1, AP>;
+        else if (poly) kern = k_bartlett_tile<8, 16, false, 0, AP>;
         PhaseClocks clk;
         if (tune_int("MMW_PHASE_CLOCKS", 0)) MMW_TRY(clk.alloc(5, ctx->stream));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, ctx->stream, (const cplx<float> *)d_X, d_P, d_dirs,
-                           (const float *)ham, Cm, S, E, T, tiles_s, NT, (int)MT, 1.0 / lambda_m, clk.d);
+                           (const float *)ham, Cm, S, E, T, tiles_s, NT, (int)MT, 1.0 / lambda_m, clk.d, ap);
         if (clk.d) {
             long long h[5] = {0};
             MMW_TRY(clk.fetch(h, 5, ctx->stream));
@@ -659,13 +706,13 @@ inline int bartlett(mmw_ctx *ctx, const void *d_X, const double *d_P, const doub
             dim3 grid((T + CG_TN - 1) / CG_TN, (S + CG_TM - 1) / CG_TM, (unsigned)(n_frames * ksplit));
             const long n_c = (long)n_frames * S * T;
             if (opt_int(ctx, "MMW_BARTLETT_BF16", 1)) {
-                MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cgemm_bf16x3), hipFuncAttributeMaxDynamicSharedMemorySize,
+                MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cgemm_bf16x3<AP>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)CB_LDS_BYTES));
-                hipLaunchKernelGGL(k_cgemm_bf16x3, grid, dim3(256), CB_LDS_BYTES, ctx->stream, (const cplx<float> *)d_X, W,
-                                   ksplit > 1 ? Cparts : Cm, S, T, E, E, Tp, T, (long)S * E, (long)E * Tp, (long)S * T, ksplit, kc, n_c);
+                hipLaunchKernelGGL(k_cgemm_bf16x3<AP>, grid, dim3(256), CB_LDS_BYTES, ctx->stream, (const cplx<float> *)d_X, W,
+                                   ksplit > 1 ? Cparts : Cm, S, T, E, E, Tp, T, (long)S * E, (long)E * Tp, (long)S * T, ksplit, kc, n_c, ap);
             } else
-                hipLaunchKernelGGL(k_cgemm_mfma, grid, dim3(256), 0, ctx->stream, (const cplx<float> *)d_X, W, ksplit > 1 ? Cparts : Cm, S, T, E,
-                                   E, Tp, T, (long)S * E, (long)E * Tp, (long)S * T, ksplit, kc, n_c);
+                hipLaunchKernelGGL(k_cgemm_mfma<AP>, grid, dim3(256), 0, ctx->stream, (const cplx<float> *)d_X, W, ksplit > 1 ? Cparts : Cm, S, T, E,
+                                   E, Tp, T, (long)S * E, (long)E * Tp, (long)S * T, ksplit, kc, n_c, ap);
             MMW_TRY(check_launch("cgemm_mfma"));
             if (ksplit > 1) {
                 hipLaunchKernelGGL(k_sum_parts, dim3((unsigned)((n_c + 255) / 256)), dim3(256), 0, ctx->stream, Cparts, Cm, n_c, ksplit);
@@ -688,11 +735,16 @@ inline int bartlett(mmw_ctx *ctx, const void *d_X, const double *d_P, const doub
     return launch_fft_axis<float, float>(ctx, a, S, false);
 }
 
+inline int bartlett(mmw_ctx *ctx, const void *d_X, const double *d_P, const double *d_dirs, void *d_out, int n_frames, int S,
+                    int E, int T, double lambda_m) {
+    return bartlett_on(ctx, ARows{}, "bartlett", d_X, d_P, d_dirs, d_out, n_frames, S, E, T, lambda_m, 0);
+}
+
 // ------------------------------------------------------------------ matrix-core peak probe (diagnostics)
 // Back-to-back MFMAs on four independent accumulators per wave, operands in registers: the rate the matrix pipe itself
 // sustains on this device, used as the `peak` the beamformer kernels are priced against (the guide lists 157.3 TF for
 // f32 MFMA and no figure for f64).  kind 0: v_mfma_f32_32x32x2_f32, 1: v_mfma_f64_16x16x4_f64.
-__global__ __launch_bounds__(256) void k_diag_mfma(float *sink, int iters, int kind) {
+static __global__ __launch_bounds__(256) void k_diag_mfma(float *sink, int iters, int kind) {
     const float seed = (float)(threadIdx.x & 7) * 0.25f + 0.5f;
     if (kind == 0) {
         v16f a0 = {0}, a1 = {0}, a2 = {0}, a3 = {0};
