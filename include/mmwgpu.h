@@ -227,6 +227,34 @@ int mmw_doppler_azimuth(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_f
  *   flags: MMW_ANGLE_NO_WINDOW, MMW_ANGLE_NO_SHIFT. */
 int mmw_doppler_azimuth_zoom(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C, int A,
                              int s_lo, int s_hi, int n_used, const double *h_freq, int M, int flags);
+/* mmw_doppler_azimuth_batch: the coarse Doppler-azimuth maps of n_sets antenna subsets of every frame of a resident batch, each
+ * frame with a range window of its own:
+ *     d_out[k][f][c][a] (float32 [n_sets][F][C][A]) = mean over rows s in [h_rows[f][0], h_rows[f][1]) of
+ *         | fftshift_A FFT_A( pad_{n->A}( hann(n)[j] RD_f[h_rx[k][j]][s][c] ) ) |,   RD = mmw_range_doppler's windowed spectrum,
+ *   i.e. DopplerAzimuthProcessor.process(cube_f[rx_k], range_window_f, shift_angle_k) before the valid-angle mask: the subset is
+ *   taken first and the Hann window spans the subset.  d_cubes [F][V][S][C] c64 as resident.  h_rx: host int32 [n_sets][n_rx];
+ *   n_rx == 0 (then n_sets == 1, V <= 16): all V antennas.  h_set_flags[n_sets]: MMW_ANGLE_NO_SHIFT per set.  flags:
+ *   MMW_ANGLE_NO_WINDOW for all sets.  h_rows: host int32 [F][2].  A frame with lo == hi gets NaN (np.mean over an empty axis).
+ *   The range-Doppler pass runs once per chunk of frames for all sets (profile family "rd"); the angle FFT, |.| and the range
+ *   mean are one kernel reading its n <= 16 inputs through the antenna list (family "dopaz_batch"); no [A][S][C] cube is written.
+ *   Intermediates stay within MMW_DOPAZ_CHUNK_MB (default 1024) per pass; a frame's result does not depend on the chunking.
+ *   MMW_ERR_INVALID (nothing launched, d_out untouched; the text names the frame / set / entry): a null pointer, n_frames < 0,
+ *   n_sets < 1, n_rx outside [0, 16], an antenna outside [0, V) or repeated within a set, a row interval outside
+ *   0 <= lo <= hi <= S, unknown flag bits, n_sets * F * C * A beyond 2^31 - 1.  MMW_ERR_UNSUPPORTED: A != 64 (the single-frame
+ *   entries take other sizes).  n_frames == 0: MMW_OK, nothing launched. */
+int mmw_doppler_azimuth_batch(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C, int A,
+                              const int32_t *h_rx, int n_sets, int n_rx, const int32_t *h_set_flags, const int32_t *h_rows, int flags);
+/* mmw_doppler_azimuth_zoom_batch: the precise (zoom) maps of the same batch, each frame with a frequency list of its own:
+ *     d_out[k][f][m][a] (float32 [n_sets][F][M][A]) = mmw_doppler_azimuth_zoom's formula on cube_f[rx_k] with rows h_rows[f] and
+ *   the list h_freq[f][0..M) (host float64 [F][M], cycles per chirp).  NaN marks a bin the reference fills with zeros and pads a
+ *   frame whose list is shorter than M: those rows of d_out are exactly 0.  n_used in [1, C] chirps enter the transform.
+ *   The range FFT runs once per chunk for all sets; the zoom transform is a direct sum on the rows of each frame's window and the
+ *   antennas some set uses, twiddles from the float64 phase (no per-list plan).  Profile family "dopaz_zoom_batch" (its phases
+ *   also under "dopaz_zoom_range", "dopaz_zoom_rows", "dopaz_zoom_mean").  Limits as mmw_doppler_azimuth_batch, with
+ *   n_sets * F * max(C, M) * A <= 2^31 - 1 and n_used outside [1, C] refused; more than 320 chirps: MMW_ERR_UNSUPPORTED. */
+int mmw_doppler_azimuth_zoom_batch(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C, int A,
+                                   const int32_t *h_rx, int n_sets, int n_rx, const int32_t *h_set_flags, const int32_t *h_rows, int flags,
+                                   int n_used, const double *h_freq, int M);
 
 /* mmw_range_profile: d_out[F][S] float32 = mean_rx | FFT_S( hann(S) x[:, :, chirp] ) |
  *   replaces RangeProcessor.coarse_fft (processors/range_resp.py:32-57).

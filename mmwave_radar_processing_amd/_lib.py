@@ -81,6 +81,8 @@ _SIGNATURES = {
     "mmw_mean_over_range": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i],
     "mmw_doppler_azimuth": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i],
     "mmw_doppler_azimuth_zoom": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_d), _i, _i],
+    "mmw_doppler_azimuth_batch": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _i, _ip, _ip, _i],
+    "mmw_doppler_azimuth_zoom_batch": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _i, _ip, _ip, _i, _i, C.POINTER(_d), _i],
     "mmw_range_profile": [_vp, _vp, _vp, _i, _i, _i, _i, _i],
     "mmw_range_profile_f64": [_vp, _vp, _vp, _i, _i, _i, _i, _i],
     "mmw_range_zoom": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d],

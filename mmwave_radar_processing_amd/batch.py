@@ -202,6 +202,48 @@ def synthetic_array_geometry(proc, velocities) -> Tuple[np.ndarray, np.ndarray]:
     return valid, (np.stack(geoms) if geoms else np.zeros((0, 3, E)))
 
 
+def _per_frame_pairs(what: str, pairs, n_frames: Optional[int]) -> np.ndarray:
+    """``[F][2]`` float64 copy of one pair for all frames or of one pair per frame."""
+    arr = np.array(pairs, dtype=np.float64)
+    if arr.shape == (2,):
+        arr = np.tile(arr, (1 if n_frames is None else n_frames, 1))
+    if arr.ndim != 2 or arr.shape[1] != 2 or (n_frames is not None and arr.shape[0] != n_frames):
+        want = "[F, 2]" if n_frames is None else f"[{n_frames}, 2] (one pair per resident frame) or one pair"
+        raise ValueError(f"doppler_azimuth: {what} must be {want}, got {arr.shape}")
+    return arr
+
+
+def doppler_azimuth_tables(proc, range_windows, precise_vel_ranges=None):
+    """Host tables of ``mmw_doppler_azimuth_batch`` / ``mmw_doppler_azimuth_zoom_batch`` for a ``DopplerAzimuthProcessor``.
+
+    ``range_windows [F, 2]`` in metres -> ``rows`` int32 ``[F, 2]``: the interval ``[lo, hi)`` of the range bins ``process`` keeps
+    for that window (``keep[0], keep[-1] + 1``; ``lo == hi`` when no bin lies inside).  With ``precise_vel_ranges [F, 2]`` the
+    result is ``(rows, freq, m, bins)``: ``freq`` float64 ``[F, M]`` the frequency list of every frame from ``proc._zoom_plan``
+    (NaN where the reference emits zeros, and NaN padding behind the ``m[f]`` bins of a frame whose list is shorter than
+    ``M = max(m)``), ``bins[f]`` that frame's ``zoomed_vel_bins``.  ``proc`` and the caller's arrays are only read."""
+    import copy
+    rb = np.asarray(proc.range_bins, dtype=np.float64)
+    rw = _per_frame_pairs("range_windows", range_windows, None)
+    lo = np.searchsorted(rb, rw[:, 0], side="left")         # first bin >= window start
+    hi = np.searchsorted(rb, rw[:, 1], side="right")        # one past the last bin <= window end
+    rows = np.stack([lo, np.maximum(hi, lo)], axis=1).astype(np.int32)
+    if precise_vel_ranges is None:
+        return rows
+    pv = _per_frame_pairs("precise_vel_ranges", precise_vel_ranges, None)
+    if len(pv) != len(rw):
+        raise ValueError(f"doppler_azimuth: {len(rw)} range windows but {len(pv)} velocity ranges")
+    plan = copy.copy(proc)              # _zoom_plan sets zoomed_vel_bins: on the copy
+    lists, bins = [], []
+    for vr in pv:
+        lists.append(np.asarray(plan._zoom_plan(vr.copy()), dtype=np.float64))
+        bins.append(np.array(plan.zoomed_vel_bins, dtype=np.float64))
+    m = np.array([len(x) for x in lists], dtype=np.int64)
+    freq = np.full((len(pv), int(m.max()) if len(m) else 0), np.nan)
+    for f, x in enumerate(lists):
+        freq[f, :len(x)] = x
+    return rows, freq, m, bins
+
+
 def _runs(flags: np.ndarray):
     """(start, stop, value) of every run of equal consecutive entries of a bool array."""
     f0 = 0
@@ -528,6 +570,93 @@ class FramePipeline:
         ``synth`` / a ``stream()`` chunk left resident; ``cfar=``, ``ground=`` and ``sequential=`` play no part."""
         d = self.micro_doppler_device(target_ranges, rx_idx)
         return d.download((self.n_frames, self.C), np.float32).astype(np.float64)
+
+    def doppler_azimuth_device(self, proc, rx_sets, range_windows, shift_angle=True, precise_vel_ranges=None):
+        """The maps of ``doppler_azimuth`` left in HBM, nothing downloaded: ``(buffer, (n_sets, F, rows, 64), m, bins)`` with the
+        buffer float32 ``[n_sets][F][rows][64]`` before the valid-angle mask, ``rows = C`` (coarse; ``m`` and ``bins`` are None) or
+        the longest frequency list of the batch (precise; frame f holds ``m[f]`` bins, zeros behind them)."""
+        from .processors.doppler_azimuth_resp import DopplerAzimuthProcessor
+        # every argument check comes before the first use of self.ctx / self.bufs
+        if not isinstance(proc, DopplerAzimuthProcessor):
+            raise ValueError(f"doppler_azimuth: proc must be a DopplerAzimuthProcessor, got {type(proc).__name__}")
+        F, V, S, C = self.n_frames, self.V, self.S, self.C
+        A = int(proc.num_angle_bins)
+        if A != 64:
+            raise ValueError(f"doppler_azimuth: the batch form is built for num_angle_bins == 64, the processor has {A}")
+        if len(proc.range_bins) != S:
+            raise ValueError(f"doppler_azimuth: cubes of {S} samples do not match the configuration's {len(proc.range_bins)} range bins")
+        sets = [np.asarray(s).astype(int).ravel() for s in rx_sets]
+        if any(len(s) != len(sets[0]) or len(s) == 0 for s in sets):
+            raise ValueError(f"doppler_azimuth: rx_sets must be antenna lists of one length, got lengths {[len(s) for s in sets]}")
+        n_sets, n_rx = max(len(sets), 1), (len(sets[0]) if sets else 0)
+        if (n_rx if sets else V) > 16:
+            raise ValueError(f"doppler_azimuth: a set holds {n_rx if sets else V} antennas: at most 16")
+        for k, s in enumerate(sets):
+            if np.any((s < -V) | (s >= V)):
+                raise ValueError(f"doppler_azimuth: rx_sets[{k}] = {s.tolist()} holds an index outside the {V} antennas")
+            if len(np.unique(s % V)) != len(s):
+                raise ValueError(f"doppler_azimuth: rx_sets[{k}] = {s.tolist()} repeats an antenna")
+        shift = np.atleast_1d(np.asarray(shift_angle, dtype=bool))
+        if shift.shape == (1,):
+            shift = np.repeat(shift, n_sets)
+        if shift.shape != (n_sets,):
+            raise ValueError(f"doppler_azimuth: shift_angle must be a bool or one per set ({n_sets}), got {shift.shape}")
+        rw = _per_frame_pairs("range_windows", range_windows, F)
+        precise = precise_vel_ranges is not None
+        m = bins = None
+        if precise:
+            pv = _per_frame_pairs("precise_vel_ranges", precise_vel_ranges, F)
+            n_used = int(proc.vel_bins.size)
+            if n_used > C:
+                raise ValueError(f"CZT defined for length {n_used}, not {C}")
+            rows, freq, m, bins = doppler_azimuth_tables(proc, rw, pv)
+            n_rows = int(freq.shape[1])
+        else:
+            rows = doppler_azimuth_tables(proc, rw)
+            n_rows = C
+        cm = proc.config_manager
+        flags = 0 if (cm.array_geometry == "standard" and cm.virtual_antennas_enabled) else _lib.ANGLE_NO_WINDOW
+        rx = np.ascontiguousarray(np.stack(sets) % V if sets else np.zeros((1, 1)), dtype=np.int32)
+        set_flags = np.ascontiguousarray(np.where(shift, 0, _lib.ANGLE_NO_SHIFT), dtype=np.int32)
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        shape = (n_sets, F, n_rows, A)
+        if F == 0 or n_rows == 0:
+            return None, shape, m, bins
+        self.d_dopaz = self.bufs.get("dopaz_batch", n_sets * F * n_rows * A * 4)
+        ip = lambda a: a.ctypes.data_as(_lib._ip)      # noqa: E731
+        lib, h = self.ctx.lib, self.ctx.handle
+        if precise:
+            freq = np.ascontiguousarray(freq, dtype=np.float64)
+            _lib.check(lib.mmw_doppler_azimuth_zoom_batch(h, self.d_in.ptr, self.d_dopaz.ptr, F, V, S, C, A, ip(rx), n_sets, n_rx,
+                                                          ip(set_flags), ip(rows), flags, n_used,
+                                                          freq.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n_rows))
+        else:
+            _lib.check(lib.mmw_doppler_azimuth_batch(h, self.d_in.ptr, self.d_dopaz.ptr, F, V, S, C, A, ip(rx), n_sets, n_rx,
+                                                     ip(set_flags), ip(rows), flags))
+        return self.d_dopaz, shape, m, bins
+
+    def doppler_azimuth(self, proc, rx_sets, range_windows, shift_angle=True, precise_vel_ranges=None):
+        """``proc.process(cube_f, rx_antennas=rx_sets[k], range_window=range_windows[f], shift_angle=shift_angle[k], ...)`` of every
+        resident frame f and antenna set k (reference: processors/doppler_azimuth_resp.py:419-491, stepped up to eight times per
+        frame by the Doppler-azimuth ego-velocity loop, processors/velocity_estimator.py:800-845), from ONE range(-Doppler) pass
+        over the resident cubes for all sets.
+
+        ``rx_sets``: equal-length antenna lists, or ``()`` for all antennas; ``range_windows``: ``[F, 2]`` metres or one pair;
+        ``shift_angle``: a bool or one per set.  Coarse mode returns float64 ``[n_sets, F, C, n_valid_angles]``; a frame whose
+        window holds no range bin is NaN.  With ``precise_vel_ranges`` (``[F, 2]`` or one pair: ``use_precise_fft=True``) the
+        result is ``(maps, zoomed_bins)``: ``zoomed_bins[f]`` are that frame's ``zoomed_vel_bins`` and its map is cut to their
+        count -- one ``[n_sets, F, m, n_valid]`` array when all frames have ``m`` bins, else a list of ``[n_sets, m_f, n_valid]``
+        arrays.  ``proc`` is only read (``proc.zoomed_vel_bins`` stays as it was).  Works on whatever ``load*`` / ``synth`` / a
+        ``stream()`` chunk left resident.  The peak pickers and the regression of the reference's estimator stay on the host."""
+        d, shape, m, bins = self.doppler_azimuth_device(proc, rx_sets, range_windows, shift_angle, precise_vel_ranges)
+        mask = np.asarray(proc.valid_angle_mask, dtype=bool)
+        full = d.download(shape, np.float32).astype(np.float64) if d is not None else np.zeros(shape)
+        full = full[..., mask]
+        if m is None:
+            return full
+        if len(m) and np.all(m == m[0]):
+            return full[:, :, :int(m[0])], bins
+        return [full[:, f, :int(m[f])] for f in range(shape[1])], bins
 
     def synthetic_array_device(self, proc, velocities) -> Tuple[np.ndarray, _lib.DeviceBuffer]:
         """``(frames, buffer)``: the images of ``synthetic_array`` left in HBM, complex64 ``[n_valid][S][n_az * n_el]``, nothing
@@ -1091,6 +1220,31 @@ class MultiDeviceFramePipeline:
         ``micro_doppler_history`` of the result is the spectrogram)."""
         rows = self._join(self._each(lambda r: self.parts[r].micro_doppler(target_ranges, rx_idx)))
         return np.asarray(rows, dtype=np.float64).reshape(self.n_frames, self.shape[2])
+
+    def doppler_azimuth(self, proc, rx_sets, range_windows, shift_angle=True, precise_vel_ranges=None):
+        """``FramePipeline.doppler_azimuth`` of every shard on its rows of the per-frame tables, joined in frame order (the frames
+        are independent of each other)."""
+        rw = _per_frame_pairs("range_windows", range_windows, self.n_frames)
+        pv = None if precise_vel_ranges is None else _per_frame_pairs("precise_vel_ranges", precise_vel_ranges, self.n_frames)
+
+        def run(r):
+            lo, hi = self.bounds[r]
+            return self.parts[r].doppler_azimuth(proc, rx_sets, rw[lo:hi], shift_angle, None if pv is None else pv[lo:hi])
+        per_rank = self._each(run)
+        if pv is None:
+            if not per_rank:
+                raise ValueError("doppler_azimuth: no frames are resident")
+            return np.concatenate(per_rank, axis=1)
+        maps, bins = [], []
+        for part_maps, part_bins in per_rank:
+            n = len(part_bins)
+            maps.extend(part_maps[:, f] if isinstance(part_maps, np.ndarray) else part_maps[f] for f in range(n))
+            bins.extend(part_bins)
+        if len(bins) != self.n_frames:
+            raise RuntimeError(f"joined {len(bins)} per-frame maps for {self.n_frames} frames")
+        if maps and all(x.shape == maps[0].shape for x in maps):
+            return np.stack(maps, axis=1), bins
+        return maps, bins
 
     def chain3d(self, magnitude: bool = False, out: Optional[np.ndarray] = None) -> Optional[np.ndarray]:
         """3-D windowed FFT of every frame on its device.  ``out`` (optional, caller-owned ``[F, A, S, C]`` complex64 /
