@@ -149,8 +149,12 @@ __device__ __forceinline__ float lane_xor1(float v) {      // the value of lane 
 // 16 bytes each: get_bigprime_bf16_table); the data operand is split on the fly.  Error budget: all SMALL partial products of
 // the 64-term sum (a1 b2, a2 b1, a1 b3, a2 b2, a3 b1: <= 2^-7 of the leading ones) are accumulated FIRST, the four MFMAs of the
 // leading pieces last, so only those 4 x 17 float32 additions round at the scale of the result: 68 + 20 x 17 x 2^-7 (small
-// phase) + 3 (dropped products) + pair sums and the combine = under 80 eps sum |x_j|, the budget rd_error_ulps() books for this
-// level in either form.  (The leading pieces of the data are formed twice -- once per phase -- instead of being kept: registers.)
+// phase) + 3 (dropped products) + pair sums and the combine = under 80 eps sum |x_j|, counted with one rounding per addition inside
+// the MFMA and no flushed bfloat16 pieces; rd_error_ulps() books a BUDGET of 88 for this level in either form.  Measured worst on
+// adversarial inputs (tests/test_gpu_rd_error_bound.py, profiles/rd_error_bound.json: impulses, coherent sums, all-ones mantissas,
+// 2^24 of dynamic range): 5.8 eps l1 for the whole 63 x 127 plane in this form, 4.6 in the float32 form, against its 132 -- a
+// measurement, not a proof of the MFMA's internal rounding.  (The leading pieces of the data are formed twice -- once per
+// phase -- instead of being kept: registers.)
 template <int P, int NT, int N_INNER, int INNER_STRIDE, int N_OUTER, int OUTER_STRIDE, int ESTRIDE, bool TW>
 __device__ __forceinline__ void dft_level_bigprime_ct(cplx<float> *lds, const cplx<float> *tw2, const float *cst, int tid,
                                                       long long *clk = nullptr, const void *abf = nullptr) {

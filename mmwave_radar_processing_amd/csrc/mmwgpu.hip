@@ -1892,6 +1892,7 @@ static int plane_l1_impl(mmw_ctx *ctx, const void *d_cubes, float *d_l1, int n_f
 //     The 127-point level of 63 x 127 / 127 x 32 / 254 x 50 is that form on MFMA tiles (64-term exact FMA chains).
 //   run-time mixed-radix kernel: its levels may be direct R-term chains: R per level on top.
 //   generic path: radix-2 levels (4 each) for powers of two, an N-term direct sum (N + 4) otherwise.
+// tests/test_rd_bound_cases_host.py restates these counts; tests/test_gpu_rd_error_bound.py asserts the inequality per family.
 static int rd_error_ulps(int S, int C) {
     auto factors = [](int n) {
         int u = 0;
@@ -2016,14 +2017,15 @@ static int launch_cells64(mmw_ctx *ctx, const RefineArgs &ra, const int32_t *d_c
 constexpr int ARGMAX_DENSE_MIXED_DEFAULT = 0;
 
 // The worst-case bound assumes every rounding error of every partial sum lines up; measured float32 errors stay below
-// 1.2 % of it (tests/argmax_margin.py: 68 000 evaluations on the 256 x 128 and 63 x 100 planes).
+// 1.2 % of it on synthetic frames (tests/argmax_margin.py: 68 000 evaluations on the 256 x 128 and 63 x 100 planes) and
+// below 7.5 % of its range-Doppler part on adversarial planes (tests/test_gpu_rd_error_bound.py, profiles/rd_error_bound.json).
 //  * mmw_detect_points (CA-CFAR detections: strong cells) uses the FULL worst-case bound with the pairwise form of the test:
 //    0.15 % of the evaluations are re-done in float64.
 //  * the stand-alone mmw_angle_argmax_exact serves the other detectors.  With the GUI's OS-CFAR parameters (rho 0.7, alpha 2:
 //    470 mostly noise-level detections per 256 x 128 frame, flat angle spectra) the full bound sends 12.8 % of the
 //    evaluations to float64 -- 120 per frame, each a direct DFT sum over whole planes: 29-36 us/frame against 7.2 with an
-//    eighth of the bound (~10x above anything observed; 1.6 % refined).  Default: 1/8 + the pairwise pass (lists of up to 8
-//    antennas); MMW_ARGMAX_BOUND_DIV=1 selects the worst case, i.e. a proof, at that price.
+//    eighth of the bound (~10x above anything observed on those frames; 1.6 % refined).  Default: the worst case (divisor 1)
+//    + the pairwise pass (lists of up to 8 antennas); MMW_ARGMAX_BOUND_DIV=8 selects the eighth again.
 static float argmax_bound_div(const mmw_ctx *ctx) { return (float)std::max(1, opt_int(ctx, "MMW_ARGMAX_BOUND_DIV", 1)); }
 
 
