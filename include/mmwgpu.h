@@ -255,6 +255,32 @@ int mmw_doppler_azimuth_batch(mmw_ctx *ctx, const void *d_cubes, float *d_out, i
 int mmw_doppler_azimuth_zoom_batch(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C, int A,
                                    const int32_t *h_rx, int n_sets, int n_rx, const int32_t *h_set_flags, const int32_t *h_rows, int flags,
                                    int n_used, const double *h_freq, int M);
+/* mmw_doppler_azimuth_peaks: DopplerAzimuthProcessor.detect_peaks_rows / detect_peak_zero_az on the maps the two batch entries
+ *   leave in HBM (or on any device buffer of that layout), for every frame and every group of sets:
+ *     d_maps float32 [n_sets][F][n_rows][A];  h_groups host int32 [G][2]: the two sets whose maps are averaged as the reference's
+ *     (resp_1 + resp_2) / 2, or (set, -1) for one set;  h_m host int32 [F]: the rows of each frame (NULL: n_rows);  the valid
+ *     angle columns [a_lo, a_hi) and the zero-azimuth column a_zero among them.
+ *     d_row_peak int32 [G][F][n_rows]: the column, relative to a_lo, of the row's strongest local maximum with at least
+ *     prominence_dB of prominence;  d_zero int32 [G][F]: the row of the strongest local maximum down column a_zero.
+ *     -1: no peak (rows >= m[f] as well);  -2: undecided.
+ *   The rule is scipy.signal.find_peaks' on the map in dB, floored min_threshold_dB below the frame's maximum, restated in the
+ *   linear domain in float64 (no log10 on the device).  A comparison of two map-derived quantities is decided only when they
+ *   are bit-equal or differ by more than the relative MMW_DOPAZ_PEAK_BAND (a quantity against a product with a dB ratio: only
+ *   when they differ by more, unless the ratio is exactly 1); otherwise the line is -2, and so is every line of a frame whose
+ *   m[f] x [a_lo, a_hi) cells hold a NaN or an Inf: the host picks those frames with the dB rule.  Profile family "dopaz_peaks".
+ *   MMW_ERR_INVALID (nothing launched, outputs untouched; the text names what was refused): a null pointer (h_m excepted), a
+ *   negative count, a group index outside [0, n_sets) or a group naming one set twice, m[f] outside [0, n_rows], a column
+ *   interval not 0 <= a_lo < a_hi <= A, a_zero outside [a_lo, a_hi), a dB parameter negative or not finite, element counts
+ *   beyond 2^31 - 1.  MMW_ERR_UNSUPPORTED: A != 64.  F == 0 or G == 0: MMW_OK, nothing launched.
+ * mmw_diag_doppler_azimuth_peaks_host: the same rule (one implementation, mmw_dopaz_peaks.h) on host pointers; no context, no
+ *   device. */
+#define MMW_DOPAZ_PEAK_BAND 1e-10
+int mmw_doppler_azimuth_peaks(mmw_ctx *ctx, const float *d_maps, int n_sets, int F, int n_rows, int A, const int32_t *h_groups, int G,
+                              const int32_t *h_m, int a_lo, int a_hi, int a_zero, double min_threshold_dB, double prominence_dB,
+                              int32_t *d_row_peak, int32_t *d_zero);
+int mmw_diag_doppler_azimuth_peaks_host(const float *h_maps, int n_sets, int F, int n_rows, int A, const int32_t *h_groups, int G,
+                                        const int32_t *h_m, int a_lo, int a_hi, int a_zero, double min_threshold_dB,
+                                        double prominence_dB, int32_t *h_row_peak, int32_t *h_zero);
 
 /* mmw_range_profile: d_out[F][S] float32 = mean_rx | FFT_S( hann(S) x[:, :, chirp] ) |
  *   replaces RangeProcessor.coarse_fft (processors/range_resp.py:32-57).

@@ -27,6 +27,8 @@ CFAR_CA, CFAR_OS, CFAR_GO, CFAR_SO = 0, 1, 2, 3
 ANGLE_MAGNITUDE, ANGLE_NO_WINDOW, ANGLE_NO_SHIFT = 1, 2, 4
 QUEUE_COMPUTE, QUEUE_COPY = 0, 1
 CELLS64_DENSE, CELLS64_DIRECT, CELLS64_DENSE_MIXED = 0, 1, 2
+DOPAZ_PEAK_BAND = 1e-10  # include/mmwgpu.h MMW_DOPAZ_PEAK_BAND: the relative band inside which the peak pickers do not decide
+DOPAZ_PEAK_NONE, DOPAZ_PEAK_UNDECIDED = -1, -2
 
 
 class MmwGpuError(RuntimeError):
@@ -83,6 +85,8 @@ _SIGNATURES = {
     "mmw_doppler_azimuth_zoom": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_d), _i, _i],
     "mmw_doppler_azimuth_batch": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _i, _ip, _ip, _i],
     "mmw_doppler_azimuth_zoom_batch": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _i, _ip, _ip, _i, _i, C.POINTER(_d), _i],
+    "mmw_doppler_azimuth_peaks": [_vp, _vp, _i, _i, _i, _i, _ip, _i, _ip, _i, _i, _i, _d, _d, _vp, _vp],
+    "mmw_diag_doppler_azimuth_peaks_host": [_vp, _i, _i, _i, _i, _ip, _i, _ip, _i, _i, _i, _d, _d, _vp, _vp],
     "mmw_range_profile": [_vp, _vp, _vp, _i, _i, _i, _i, _i],
     "mmw_range_profile_f64": [_vp, _vp, _vp, _i, _i, _i, _i, _i],
     "mmw_range_zoom": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d],

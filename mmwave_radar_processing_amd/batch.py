@@ -244,6 +244,51 @@ def doppler_azimuth_tables(proc, range_windows, precise_vel_ranges=None):
     return rows, freq, m, bins
 
 
+def _peak_groups(groups, n_sets: int, shift: np.ndarray) -> np.ndarray:
+    """``[G][2]`` int32 table of ``mmw_doppler_azimuth_peaks`` from groups written as a set index, ``(set,)`` or ``(set, set)``."""
+    table = []
+    for g, grp in enumerate(groups):
+        idx = [int(i) for i in np.atleast_1d(np.asarray(grp)).ravel()]
+        if len(idx) not in (1, 2):
+            raise ValueError(f"doppler_azimuth_peaks: groups[{g}] = {grp!r} must name one set or two")
+        if any(not 0 <= i < n_sets for i in idx):
+            raise ValueError(f"doppler_azimuth_peaks: groups[{g}] = {grp!r} names a set outside the {n_sets} of rx_sets")
+        if len(idx) == 2 and idx[0] == idx[1]:
+            raise ValueError(f"doppler_azimuth_peaks: groups[{g}] = {grp!r} names one set twice")
+        if len(idx) == 2 and shift[idx[0]] != shift[idx[1]]:
+            raise ValueError(f"doppler_azimuth_peaks: groups[{g}] = {grp!r} averages sets that do not share shift_angle")
+        table.append(idx + [-1] * (2 - len(idx)))
+    return np.array(table, dtype=np.int32).reshape(len(table), 2)
+
+
+def precise_ranges_from_zero_az(az_zero, el_zero, precise_vel_bound: float = 0.25) -> np.ndarray:
+    """The ``[F, 2]`` velocity ranges of the precise pass from the zero-azimuth peaks of a coarse pass: per frame the reference's
+    ``estimate_ego_vx_velocity`` (processors/velocity_estimator.py:640-661: minus the mean of the azimuth and the elevation peak
+    velocity when both exist, minus the one that exists, else 0) and the ``precise_vel_range`` its ``compute_*_response`` build
+    around ``-1 * ego_vx`` (:163-166).  ``az_zero[f]`` / ``el_zero[f]``: what ``detect_peak_zero_az`` returns (``[0.0, vel]`` or an
+    empty ``(0, 2)`` array); ``el_zero=None``: no elevation response (a standard array).  Host only."""
+    def vels(peaks, n):
+        out = np.full(n, np.nan)
+        for f, p in enumerate(peaks):
+            p = np.asarray(p, dtype=np.float64)
+            if p.shape[0] > 0:
+                out[f] = p[1]
+        return out
+    n = len(az_zero)
+    if el_zero is not None and len(el_zero) != n:
+        raise ValueError(f"precise_ranges_from_zero_az: {n} azimuth peaks but {len(el_zero)} elevation peaks")
+    az = vels(az_zero, n)
+    el = vels(el_zero, n) if el_zero is not None else np.full(n, np.nan)
+    has_az, has_el = ~np.isnan(az), ~np.isnan(el)
+    ego = np.zeros(n)
+    both = has_az & has_el
+    ego[both] = -1 * (az[both] + el[both]) / 2.0
+    ego[has_az & ~has_el] = -1 * az[has_az & ~has_el]
+    ego[has_el & ~has_az] = -1 * el[has_el & ~has_az]
+    centre = -1 * ego
+    return np.stack([centre - precise_vel_bound, centre + precise_vel_bound], axis=1)
+
+
 def _runs(flags: np.ndarray):
     """(start, stop, value) of every run of equal consecutive entries of a bool array."""
     f0 = 0
@@ -647,7 +692,8 @@ class FramePipeline:
         result is ``(maps, zoomed_bins)``: ``zoomed_bins[f]`` are that frame's ``zoomed_vel_bins`` and its map is cut to their
         count -- one ``[n_sets, F, m, n_valid]`` array when all frames have ``m`` bins, else a list of ``[n_sets, m_f, n_valid]``
         arrays.  ``proc`` is only read (``proc.zoomed_vel_bins`` stays as it was).  Works on whatever ``load*`` / ``synth`` / a
-        ``stream()`` chunk left resident.  The peak pickers and the regression of the reference's estimator stay on the host."""
+        ``stream()`` chunk left resident.  ``doppler_azimuth_peaks`` picks the peaks of these maps on the device; the regression of
+        the reference's estimator stays on the host."""
         d, shape, m, bins = self.doppler_azimuth_device(proc, rx_sets, range_windows, shift_angle, precise_vel_ranges)
         mask = np.asarray(proc.valid_angle_mask, dtype=bool)
         full = d.download(shape, np.float32).astype(np.float64) if d is not None else np.zeros(shape)
@@ -657,6 +703,98 @@ class FramePipeline:
         if len(m) and np.all(m == m[0]):
             return full[:, :, :int(m[0])], bins
         return [full[:, f, :int(m[f])] for f in range(shape[1])], bins
+
+    def doppler_azimuth_peaks_device(self, proc, rx_sets, groups, range_windows, shift_angle=True, precise_vel_ranges=None,
+                                     min_threshold_dB=30.0):
+        """``doppler_azimuth_device`` and then ``mmw_doppler_azimuth_peaks`` on the maps it left in HBM; only the two index tables
+        are downloaded: ``(row_peak, zero, m, bins)`` with ``row_peak`` int32 ``[G, F, rows]`` (the column among the valid angle
+        bins of each row's peak), ``zero`` int32 ``[G, F]`` (the row of the zero-azimuth peak); -1: none, -2: undecided.
+        ``self.dopaz_peak_maps`` keeps ``(buffer, shape)`` of the maps for the frames the host has to pick again."""
+        # every argument check comes before the first use of self.ctx / self.bufs
+        n_sets = max(len(rx_sets), 1)
+        shift = np.atleast_1d(np.asarray(shift_angle, dtype=bool))
+        if shift.shape == (1,):
+            shift = np.repeat(shift, n_sets)
+        if shift.shape != (n_sets,):
+            raise ValueError(f"doppler_azimuth: shift_angle must be a bool or one per set ({n_sets}), got {shift.shape}")
+        table = _peak_groups(groups, n_sets, shift)
+        thr = float(min_threshold_dB)
+        if not (np.isfinite(thr) and thr >= 0.0):
+            raise ValueError(f"doppler_azimuth_peaks: min_threshold_dB must be finite and non-negative, got {min_threshold_dB}")
+        valid = np.flatnonzero(np.asarray(getattr(proc, "valid_angle_mask", True), dtype=bool))   # another proc: refused below
+        if valid.size == 0 or not np.array_equal(valid, np.arange(valid[0], valid[-1] + 1)):
+            raise ValueError("doppler_azimuth_peaks: the valid angle bins must be one non-empty run of columns")
+        d, shape, m, bins = self.doppler_azimuth_device(proc, rx_sets, range_windows, shift_angle, precise_vel_ranges)
+        _, F, n_rows, A = shape
+        G = len(table)
+        row_peak = np.full((G, F, n_rows), _lib.DOPAZ_PEAK_NONE, dtype=np.int32)
+        zero = np.full((G, F), _lib.DOPAZ_PEAK_NONE, dtype=np.int32)
+        self.dopaz_peak_maps = (d, shape)
+        if d is None or G == 0:
+            return row_peak, zero, m, bins
+        a_lo, a_hi = int(valid[0]), int(valid[-1]) + 1
+        a_zero = a_lo + int(np.argmin(np.abs(proc.valid_angle_bins)))
+        d_row = self.bufs.get("dopaz_row_peak", row_peak.nbytes)
+        d_zero = self.bufs.get("dopaz_zero_peak", zero.nbytes)
+        ip = lambda a: a.ctypes.data_as(_lib._ip)      # noqa: E731
+        h_m = None if m is None else np.ascontiguousarray(m, dtype=np.int32)
+        _lib.check(self.ctx.lib.mmw_doppler_azimuth_peaks(self.ctx.handle, d.ptr, shape[0], F, n_rows, A, ip(table), G,
+                                                          None if h_m is None else ip(h_m), a_lo, a_hi, a_zero, thr, 4.0,
+                                                          d_row.ptr, d_zero.ptr))
+        return d_row.download(row_peak.shape, np.int32), d_zero.download(zero.shape, np.int32), m, bins
+
+    def doppler_azimuth_peaks(self, proc, rx_sets, groups, range_windows, shift_angle=True, precise_vel_ranges=None,
+                              min_threshold_dB=30.0):
+        """The peak pickers of the reference's Doppler-azimuth velocity loop (processors/velocity_estimator.py:785-865) on the maps
+        of ``doppler_azimuth``, picked on the device: ``(row_peaks, zero_az)`` with ``row_peaks[g][f]`` what
+        ``proc.detect_peaks_rows(map, vel_bins, min_threshold_dB)`` returns for frame f's map of ``groups[g]`` -- one set's map, or
+        the mean of two sets' maps (``(resp_1 + resp_2) / 2``) -- and ``zero_az[g][f]`` what ``proc.detect_peak_zero_az`` returns;
+        ``vel_bins`` are ``proc.vel_bins``, or the frame's ``zoomed_vel_bins`` with ``precise_vel_ranges``.
+
+        ``groups``: per group a set index, ``(set,)`` or ``(set, set)`` into ``rx_sets``; two sets must share ``shift_angle``.
+        Frames the device left undecided (a comparison inside ``MMW_DOPAZ_PEAK_BAND``, a non-finite map such as that of an empty
+        range window) are picked by the host pickers from that frame's downloaded maps; ``self.n_peaks_undecided`` counts them
+        per (group, frame).  A precise frame without velocity bins yields empty results.  The other arguments are those of
+        ``doppler_azimuth``; ``proc`` is only read."""
+        row_peak, zero, m, bins = self.doppler_azimuth_peaks_device(proc, rx_sets, groups, range_windows, shift_angle,
+                                                                    precise_vel_ranges, min_threshold_dB)
+        d, shape = self.dopaz_peak_maps
+        G, F, n_rows = row_peak.shape
+        valid_bins = np.asarray(proc.valid_angle_bins, dtype=np.float64)
+        mask = np.asarray(proc.valid_angle_mask, dtype=bool)
+        if m is None:
+            rows_of = np.full(F, n_rows, dtype=np.int64)
+            vel = np.broadcast_to(np.asarray(proc.vel_bins, dtype=np.float64), (F, n_rows))
+        else:
+            rows_of = np.asarray(m, dtype=np.int64)
+            vel = np.zeros((F, n_rows))
+            for f in range(F):
+                vel[f, :rows_of[f]] = bins[f]
+        # every decided peak of the batch at once, then cut into its (group, frame) pieces
+        found = row_peak >= 0
+        _, f_idx, r_idx = np.nonzero(found)
+        pairs = np.stack([valid_bins[row_peak[found]], vel[f_idx, r_idx]], axis=1)
+        pieces = np.split(pairs, np.cumsum(found.sum(axis=2).ravel())[:-1]) if G * F else []
+        undecided = (np.any(row_peak == _lib.DOPAZ_PEAK_UNDECIDED, axis=2) | (zero == _lib.DOPAZ_PEAK_UNDECIDED)) & (rows_of > 0)[None, :]
+        table = _peak_groups(groups, shape[0], np.zeros(shape[0], dtype=bool))
+        row_peaks, zero_az = [], []
+        for g in range(G):
+            row_peaks.append([])
+            zero_az.append([])
+            for f in range(F):
+                if undecided[g, f]:
+                    frame_bytes = n_rows * shape[3] * 4
+                    sets = [d.download((n_rows, shape[3]), np.float32, (int(k) * F + f) * frame_bytes).astype(np.float64)
+                            for k in table[g] if k >= 0]
+                    resp = (sets[0] if len(sets) == 1 else (sets[0] + sets[1]) / 2)[:rows_of[f], mask]
+                    row_peaks[g].append(proc.detect_peaks_rows(resp, vel[f, :rows_of[f]], min_threshold_dB))
+                    zero_az[g].append(proc.detect_peak_zero_az(resp, vel[f, :rows_of[f]], min_threshold_dB))
+                    continue
+                row_peaks[g].append(pieces[g * F + f])
+                z = int(zero[g, f])
+                zero_az[g].append(np.array([0.0, vel[f, z]]) if z >= 0 else np.empty(shape=(0, 2)))
+        self.n_peaks_undecided = int(undecided.sum())
+        return row_peaks, zero_az
 
     def synthetic_array_device(self, proc, velocities) -> Tuple[np.ndarray, _lib.DeviceBuffer]:
         """``(frames, buffer)``: the images of ``synthetic_array`` left in HBM, complex64 ``[n_valid][S][n_az * n_el]``, nothing
@@ -1245,6 +1383,28 @@ class MultiDeviceFramePipeline:
         if maps and all(x.shape == maps[0].shape for x in maps):
             return np.stack(maps, axis=1), bins
         return maps, bins
+
+    def doppler_azimuth_peaks(self, proc, rx_sets, groups, range_windows, shift_angle=True, precise_vel_ranges=None,
+                              min_threshold_dB=30.0):
+        """``FramePipeline.doppler_azimuth_peaks`` of every shard on its rows of the per-frame tables; the per-frame lists of every
+        group joined in frame order.  ``n_peaks_undecided`` is the sum over the shards."""
+        rw = _per_frame_pairs("range_windows", range_windows, self.n_frames)
+        pv = None if precise_vel_ranges is None else _per_frame_pairs("precise_vel_ranges", precise_vel_ranges, self.n_frames)
+
+        def run(r):
+            lo, hi = self.bounds[r]
+            part = self.parts[r]
+            res = part.doppler_azimuth_peaks(proc, rx_sets, groups, rw[lo:hi], shift_angle, None if pv is None else pv[lo:hi],
+                                             min_threshold_dB)
+            return res, part.n_peaks_undecided
+        per_rank = self._each(run)
+        if not per_rank:
+            raise ValueError("doppler_azimuth_peaks: no frames are resident")
+        G = len(per_rank[0][0][0])
+        row_peaks = [self._join([res[0][g] for res, _ in per_rank]) for g in range(G)]
+        zero_az = [self._join([res[1][g] for res, _ in per_rank]) for g in range(G)]
+        self.n_peaks_undecided = sum(n for _, n in per_rank)
+        return row_peaks, zero_az
 
     def chain3d(self, magnitude: bool = False, out: Optional[np.ndarray] = None) -> Optional[np.ndarray]:
         """3-D windowed FFT of every frame on its device.  ``out`` (optional, caller-owned ``[F, A, S, C]`` complex64 /

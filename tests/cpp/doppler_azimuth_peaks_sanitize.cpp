@@ -1,0 +1,144 @@
+// The host code of mmw_doppler_azimuth_peaks / mmw_diag_doppler_azimuth_peaks_host under AddressSanitizer +
+// UndefinedBehaviorSanitizer, as a program of its own: the translation unit mmw_tu_dopaz_peaks.hip compiled host-only (the kernel
+// becomes a launch stub that is never reached here) and linked with this driver.  Both entries judge every argument before the
+// device entry touches its context, so a context that is never dereferenced stands in for a real one: each class of refused
+// argument must come back as MMW_ERR_INVALID (A != 64: MMW_ERR_UNSUPPORTED) with an error text that names what was refused and
+// with the sentinel-filled outputs untouched, and F == 0 / G == 0 as MMW_OK, without a device.  The host arrays are exactly as
+// long as the entries are told.  The host-only entry then runs the shared rule on small maps (a plateau, a short frame, a NaN
+// frame) under the sanitizers.  mmw_last_error's storage and the one function of another unit the plumbing refers to are
+// supplied here.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../include/mmwgpu.h"
+#include "../../mmwave_radar_processing_amd/csrc/mmw_ctx.h"
+
+namespace mmw {
+int chain_settle(mmw_ctx *) { return MMW_OK; }      // mmwgpu.hip's; only reached through a context with chain work pending
+}  // namespace mmw
+
+static int fails = 0, calls = 0;
+#define CHECK(cond)                                                          \
+    do {                                                                     \
+        ++calls;                                                             \
+        if (!(cond)) {                                                       \
+            std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
+            ++fails;                                                         \
+        }                                                                    \
+    } while (0)
+
+static bool refused(int rc, const char *names = nullptr, int code = MMW_ERR_INVALID) {
+    const bool ok = rc == code && !mmw::g_last_error.empty() && (!names || std::strstr(mmw::g_last_error.c_str(), names));
+    if (!ok) std::fprintf(stderr, "  rc %d, text '%s'\n", rc, mmw::g_last_error.c_str());
+    mmw::g_last_error.clear();
+    return ok;
+}
+
+constexpr int32_t SENTINEL = -77;
+
+struct Args {
+    mmw_ctx *ctx;
+    int n_sets = 4, F = 3, n_rows = 5, A = 64, G = 3;
+    std::vector<float> maps = std::vector<float>((size_t)4 * 3 * 5 * 64, 1.0f);
+    std::vector<int32_t> groups{0, 1, 2, -1, 3, 2}, m{5, 0, 3};
+    int a_lo = 4, a_hi = 60, a_zero = 32;
+    double thr = 30.0, prom = 4.0;
+    std::vector<int32_t> row = std::vector<int32_t>((size_t)3 * 3 * 5, SENTINEL), zero = std::vector<int32_t>((size_t)3 * 3, SENTINEL);
+    bool no_maps = false, no_groups = false, no_m = false, no_row = false, no_zero = false;
+};
+
+static bool untouched(const Args &a) {
+    for (int32_t v : a.row) if (v != SENTINEL) return false;
+    for (int32_t v : a.zero) if (v != SENTINEL) return false;
+    return true;
+}
+
+// the device entry (the maps and the outputs are then device pointers it never reaches) or the host-only one
+static int run(Args &a, bool device) {
+    const float *maps = a.no_maps ? nullptr : a.maps.data();
+    const int32_t *groups = a.no_groups ? nullptr : a.groups.data(), *m = a.no_m ? nullptr : a.m.data();
+    int32_t *row = a.no_row ? nullptr : a.row.data(), *zero = a.no_zero ? nullptr : a.zero.data();
+    if (device)
+        return mmw_doppler_azimuth_peaks(a.ctx, maps, a.n_sets, a.F, a.n_rows, a.A, groups, a.G, m, a.a_lo, a.a_hi, a.a_zero, a.thr,
+                                         a.prom, row, zero);
+    return mmw_diag_doppler_azimuth_peaks_host(maps, a.n_sets, a.F, a.n_rows, a.A, groups, a.G, m, a.a_lo, a.a_hi, a.a_zero, a.thr, a.prom,
+                                               row, zero);
+}
+
+#define REFUSED(a, ...) CHECK(refused(run(a, device), __VA_ARGS__) && untouched(a))
+
+int main() {
+    // never dereferenced: every call of the device entry below ends in dzp_validate, which is not given the context, or at the
+    // F == 0 / G == 0 return right behind it
+    alignas(64) static unsigned char ctx_bytes[64];
+    Args good;
+    good.ctx = reinterpret_cast<mmw_ctx *>(ctx_bytes);
+    for (bool device : {true, false}) {
+        Args a = good;
+        // null pointers (h_m may be null: every frame has n_rows rows)
+        if (device) { a.ctx = nullptr; REFUSED(a, "null"); a = good; }
+        a.no_maps = true; REFUSED(a, "null"); a = good;
+        a.no_groups = true; REFUSED(a, "null"); a = good;
+        a.no_row = true; REFUSED(a, "null"); a = good;
+        a.no_zero = true; REFUSED(a, "null"); a = good;
+        // negative counts
+        for (int n : {-1, -2147483647 - 1}) {
+            a.n_sets = n; REFUSED(a, "negative count"); a = good;
+            a.F = n; REFUSED(a, "negative count"); a = good;
+            a.n_rows = n; REFUSED(a, "negative count"); a = good;
+            a.G = n; REFUSED(a, "negative count"); a = good;
+        }
+        for (int n : {0, -1}) { a.A = n; REFUSED(a, "angle bins"); a = good; }
+        // groups: an index outside [0, n_sets), one set twice -- the text names the group
+        for (int s : {-1, 4, 2147483647, -2147483647 - 1}) { a.groups[2] = s; REFUSED(a, "group 1"); a = good; }
+        for (int s : {-2, 4, 2147483647, -2147483647 - 1}) { a.groups[5] = s; REFUSED(a, "group 2"); a = good; }
+        a.groups[1] = 0; REFUSED(a, "group 0 names set 0 twice"); a = good;
+        a.n_sets = 0; REFUSED(a, "group 0"); a = good;
+        // rows of a frame -- the text names the frame
+        for (int m : {-1, 6, 2147483647, -2147483647 - 1}) { a.m[2] = m; REFUSED(a, "frame 2"); a = good; }
+        // the column interval and the zero column
+        const int bad_cols[][2] = {{-1, 10}, {10, 10}, {11, 10}, {0, 65}, {64, 64}, {2147483647, -2147483647 - 1}};
+        for (auto &c : bad_cols) { a.a_lo = c[0], a.a_hi = c[1]; REFUSED(a, "column interval"); a = good; }
+        for (int z : {3, 60, -1, 2147483647}) { a.a_zero = z; REFUSED(a, "a_zero"); a = good; }
+        // the dB parameters
+        for (double v : {-1.0, -0.0001, (double)NAN, (double)INFINITY, -(double)INFINITY}) {
+            a.thr = v; REFUSED(a, "min_threshold_dB"); a = good;
+            a.prom = v; REFUSED(a, "prominence_dB"); a = good;
+        }
+        // the element index
+        { Args b = good; b.F = 2000000; b.n_rows = 20; b.no_m = true; REFUSED(b, "32-bit"); }
+        // other angle sizes: no kernel
+        for (int A : {32, 128}) { a.A = A; a.a_hi = 30, a.a_zero = 16; REFUSED(a, "64 angle bins", MMW_ERR_UNSUPPORTED); a = good; }
+        // no frames / no groups: a successful no-op; it does not excuse a bad argument
+        if (device) {
+            a.F = 0; a.m.clear(); a.m.reserve(1); CHECK(run(a, device) == MMW_OK && mmw::g_last_error.empty() && untouched(a));
+            a.a_zero = 61; REFUSED(a, "a_zero"); a = good;
+            a.G = 0; a.groups.clear(); a.groups.reserve(1); CHECK(run(a, device) == MMW_OK && mmw::g_last_error.empty() && untouched(a));
+            a.thr = -3.0; REFUSED(a, "min_threshold_dB"); a = good;
+        }
+    }
+    // the shared rule on the host: a plateau peak, a short frame with data behind it, a frame with a NaN
+    {
+        Args a = good;
+        float *x = a.maps.data();
+        auto at = [&](int s, int f, int r, int c) -> float & { return x[(((size_t)s * a.F + f) * a.n_rows + r) * 64 + c]; };
+        for (int s = 0; s < 4; ++s) {
+            at(s, 0, 1, 10) = at(s, 0, 1, 11) = at(s, 0, 1, 12) = 8.0f;      // a plateau of three: its middle
+            at(s, 0, 2, 32) = 6.0f;
+            at(s, 2, 1, 32) = 5.0f;
+            at(s, 2, 3, 32) = at(s, 2, 4, 32) = 100.0f;                       // behind m[2] == 3
+        }
+        at(3, 0, 0, 4) = NAN;                                                 // groups 2 = (3, 2): undecided in frame 0
+        CHECK(run(a, false) == MMW_OK);
+        auto row = [&](int g, int f, int r) { return a.row[((size_t)g * a.F + f) * a.n_rows + r]; };
+        CHECK(row(0, 0, 1) == 11 - 4 && row(0, 0, 2) == 32 - 4 && row(0, 0, 0) == -1 && a.zero[0] == 2);
+        CHECK(row(2, 0, 1) == -2 && row(2, 0, 4) == -2 && a.zero[2 * 3 + 0] == -2);
+        for (int r = 0; r < 5; ++r) CHECK(row(1, 1, r) == -1);                // m[1] == 0
+        CHECK(a.zero[1 * 3 + 1] == -1);
+        CHECK(row(1, 2, 1) == 32 - 4 && row(1, 2, 3) == -1 && row(1, 2, 4) == -1 && a.zero[1 * 3 + 2] == 1);
+    }
+    std::printf("doppler_azimuth_peaks_sanitize: %d checks, %d failures\n", calls, fails);
+    return fails ? 1 : 0;
+}
