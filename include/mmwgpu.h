@@ -499,7 +499,11 @@ int mmw_rd_cells64_at(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_dets, 
  *   angles (:543-585) becomes one complex GEMM per frame.
  * mmw_capon: MVDR spectrum on a V-element half-wavelength ULA for a batch of frames; NO upstream implementation
  *   exists -- definition in DESIGN.md; d_X [F][V][R][K] c64 (K snapshots per range bin),
- *   d_out [F][R][T] float32. */
+ *   d_out [F][R][T] float32.  h_thetas: T angles in radians, host memory, read during the call.  MMW_ERR_INVALID, with
+ *   d_out untouched, for a null pointer, n_frames < 0, V outside 1..16, R, K or T < 1, and a delta that is negative,
+ *   NaN or infinite; n_frames == 0 returns MMW_OK and writes nothing.  delta == 0 with K < V is accepted (the sample
+ *   covariance is singular there and the result is not a number the definition gives).  A bin that holds a NaN or an
+ *   Inf gives non-finite values in that bin's T outputs only. */
 int mmw_bartlett(mmw_ctx *ctx, const void *d_X, const double *d_P, const double *d_dirs,
                  void *d_out, int n_frames, int S, int E, int T, double lambda_m);
 int mmw_capon(mmw_ctx *ctx, const void *d_X, const double *h_thetas, float *d_out,

@@ -2877,6 +2877,7 @@ int mmw_capon(mmw_ctx *ctx, const void *d_X, const double *h_thetas, float *d_ou
     MMW_REQUIRE(ctx && d_X && h_thetas && d_out, "null argument");
     MMW_JOIN(ctx);
     MMW_REQUIRE(n_frames >= 0 && V > 0 && V <= 16 && R > 0 && K > 0 && T > 0, "bad shape (V <= 16)");
+    MMW_REQUIRE(delta >= 0.0 && std::isfinite(delta), "diagonal loading %g is not a finite number >= 0", delta);
     if (n_frames == 0) return MMW_OK;
     return capon(ctx, d_X, h_thetas, d_out, n_frames, V, R, K, T, delta);
 }
