@@ -508,6 +508,21 @@ int mmw_bartlett(mmw_ctx *ctx, const void *d_X, const double *d_P, const double 
                  void *d_out, int n_frames, int S, int E, int T, double lambda_m);
 int mmw_capon(mmw_ctx *ctx, const void *d_X, const double *h_thetas, float *d_out,
               int n_frames, int V, int R, int K, int T, double delta);
+/* mmw_range_snapshots: the snapshots mmw_capon takes as d_X, made from resident cubes d_cubes [F][V][S][C] c64:
+ *     d_out[f][i][r - r_lo][k] (complex64, [F][n_rx][r_hi - r_lo][C]) =
+ *         sum_s w[s] * x[f][h_rx[i]][s][k] * exp(-2 pi j r s / S),   r_lo <= r < r_hi, every chirp k,
+ *     w = np.hanning(S) (the table mmw_range_profile uses) when perform_windowing, else 1.
+ *   n_rx == 0: all V antennas in order (as mmw_range_angle); an index may occur more than once in h_rx (host memory, read
+ *   during the call).  No upstream implementation exists: the range FFT of every chirp, left in place, is the
+ *   [V][R = S][K = C] snapshot tensor of the Capon definition in DESIGN.md.  float32 arithmetic, tables made in float64 on the
+ *   host; only the rows of the window are written.  A power-of-two S from 16 to 1024 runs register FFTs with one LDS exchange,
+ *   every other S up to 1024 a direct partial DFT whose twiddle index is (r s) mod S in integers.
+ *   MMW_ERR_INVALID (nothing launched, d_out untouched; the text names what was refused): a null ctx, d_cubes or d_out,
+ *   n_frames < 0, V, S or C < 1, n_rx < 0, n_rx > 0 with a null h_rx, a listed index outside [0, V), a window that is not
+ *   0 <= r_lo < r_hi <= S.  MMW_ERR_UNSUPPORTED (nothing launched): S > 1024, or more than 2^31 - 1 workgroups in a launch.
+ *   n_frames == 0: MMW_OK, nothing written.  Profile family "range_snapshots". */
+int mmw_range_snapshots(mmw_ctx *ctx, const void *d_cubes, void *d_out, int n_frames, int V, int S, int C,
+                        const int *h_rx, int n_rx, int r_lo, int r_hi, int perform_windowing);
 
 /* ---------------------------------------------------------------- element-wise helpers */
 int mmw_abs_c64(mmw_ctx *ctx, const void *d_in, float *d_out, size_t n);

@@ -17,6 +17,8 @@ from . import _lib
 from .detectors.base import BaseCFAR1D
 from .detectors.ca_cfar import CaCFAR2D
 from .processors.range_angle_resp import angle_tables
+from .processors.steering_beamformers import (CAPON_PASS_BUDGET, capon_cube_args, capon_from_cubes,  # noqa: F401
+                                              capon_pass_frames, capon_passes)
 
 
 def shard_bounds(n_frames: int, rank: int, world: int) -> Tuple[int, int]:
@@ -615,6 +617,42 @@ class FramePipeline:
         ``synth`` / a ``stream()`` chunk left resident; ``cfar=``, ``ground=`` and ``sequential=`` play no part."""
         d = self.micro_doppler_device(target_ranges, rx_idx)
         return d.download((self.n_frames, self.C), np.float32).astype(np.float64)
+
+    def capon_range_angle_device(self, thetas_rad, rx_antennas, range_bins=None, delta: float = 1e-3,
+                                 perform_windowing: bool = True, frames_per_pass: Optional[int] = None) -> _lib.DeviceBuffer:
+        """The Capon maps of ``capon_range_angle`` left in HBM: float32 ``[n_frames][R_w][T]``, nothing downloaded."""
+        # every argument check comes before the first use of self.ctx / self.bufs
+        th, rx, (r_lo, r_hi), delta, fpp = capon_cube_args(self.V, self.S, thetas_rad, rx_antennas, range_bins, delta,
+                                                           frames_per_pass)
+        F, Rw, T = self.n_frames, r_hi - r_lo, len(th)
+        if fpp is None:
+            fpp = capon_pass_frames(len(rx), Rw, self.C)
+        fpp = max(1, min(fpp, F))
+        self._capon_shape = (F, Rw, T)
+        self.d_capon = self.bufs.get("capon_ra", max(F, 1) * Rw * T * 4)
+        d_snap = self.bufs.get("capon_snap", fpp * len(rx) * Rw * self.C * 8)
+        capon_from_cubes(self.ctx, self.d_in.ptr, d_snap, self.d_capon, F, (self.V, self.S, self.C), th, rx, (r_lo, r_hi), delta,
+                         perform_windowing, fpp)
+        return self.d_capon
+
+    def capon_range_angle(self, thetas_rad, rx_antennas, range_bins=None, delta: float = 1e-3, perform_windowing: bool = True,
+                          frames_per_pass: Optional[int] = None) -> np.ndarray:
+        """Capon / MVDR range-azimuth map of every resident frame, float64 ``[n_frames, R_w, T]``: row ``r - r_lo`` of frame f
+        is ``CaponBeamformer(thetas_rad, delta).process(X_f)[r - r_lo]`` on the snapshots ``X_f[i][r - r_lo][k]`` = bin r of the
+        (Hann-windowed, unless ``perform_windowing=False``) range FFT of chirp k of antenna ``rx_antennas[i]`` -- with the
+        snapshots made on the device from the resident cubes instead of on the host (no upstream implementation exists; the
+        definition is DESIGN.md 4.20).  ``rx_antennas``: the ordered azimuth row of the virtual array, 1..16 indices, a
+        half-wavelength uniform line array in list order.  ``range_bins=(r_lo, r_hi)``: bin indices, default the whole profile.
+
+        Two calls per pass of ``frames_per_pass`` frames (default ``capon_pass_frames``: a 1 GiB snapshot budget, the fastest
+        of the pass sizes measured in DESIGN.md 4.20), on the context's queue in order:
+        ``mmw_range_snapshots`` into one scratch buffer, ``mmw_capon`` from it into the pass's slice of the result.  A frame's
+        map does not depend on the pass it is in.  Works on whatever ``load`` / ``load_raw`` / ``load_raw_i16`` / ``synth`` / a
+        ``stream()`` chunk left resident; ``cfar=``, ``ground=`` and ``sequential=`` play no part."""
+        d = self.capon_range_angle_device(thetas_rad, rx_antennas, range_bins, delta, perform_windowing, frames_per_pass)
+        if self.n_frames == 0:
+            return np.zeros(self._capon_shape)
+        return d.download(self._capon_shape, np.float32).astype(np.float64)
 
     def doppler_azimuth_device(self, proc, rx_sets, range_windows, shift_angle=True, precise_vel_ranges=None):
         """The maps of ``doppler_azimuth`` left in HBM, nothing downloaded: ``(buffer, (n_sets, F, rows, 64), m, bins)`` with the
@@ -1358,6 +1396,17 @@ class MultiDeviceFramePipeline:
         ``micro_doppler_history`` of the result is the spectrogram)."""
         rows = self._join(self._each(lambda r: self.parts[r].micro_doppler(target_ranges, rx_idx)))
         return np.asarray(rows, dtype=np.float64).reshape(self.n_frames, self.shape[2])
+
+    def capon_range_angle(self, thetas_rad, rx_antennas, range_bins=None, delta: float = 1e-3, perform_windowing: bool = True,
+                          frames_per_pass: Optional[int] = None) -> np.ndarray:
+        """``FramePipeline.capon_range_angle`` of every shard on its own frames, concatenated in frame order (a frame's map does
+        not depend on the other frames)."""
+        th, _, (r_lo, r_hi), _, _ = capon_cube_args(self.shape[0], self.shape[1], thetas_rad, rx_antennas, range_bins, delta,
+                                                    frames_per_pass)
+        per_rank = self._each(lambda r: self.parts[r].capon_range_angle(thetas_rad, rx_antennas, range_bins, delta,
+                                                                        perform_windowing, frames_per_pass))
+        maps = self._join([np.asarray(p, dtype=np.float64) for p in per_rank])
+        return np.asarray(maps, dtype=np.float64).reshape(self.n_frames, r_hi - r_lo, len(th))
 
     def doppler_azimuth(self, proc, rx_sets, range_windows, shift_angle=True, precise_vel_ranges=None):
         """``FramePipeline.doppler_azimuth`` of every shard on its rows of the per-frame tables, joined in frame order (the frames

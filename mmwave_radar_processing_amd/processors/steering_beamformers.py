@@ -79,6 +79,85 @@ class SyntheticArrayBeamformerCore:
         return self.beamformed_resp
 
 
+# Bytes of snapshots per pass.  Measured (profiles/capon_range_angle.json): 1024 MiB is the fastest of 16 / 64 /
+# 256 / 1024 MiB and a single pass on both bench shapes; 256 MiB is within 1 % of it, the 64 MiB first guessed (a quarter of the
+# Infinity Cache) 4-9 % slower, 16 MiB 1.8-2.4 times slower: the launches of a short pass do not fill the chip.
+CAPON_PASS_BUDGET = 1024 << 20
+
+
+def capon_pass_frames(n_rx: int, n_rows: int, C: int, budget_bytes: int = CAPON_PASS_BUDGET) -> int:
+    """Frames per pass of ``capon_range_angle``: the largest count whose complex64 snapshot tensor ``[n][n_rx][n_rows][C]`` fits
+    ``budget_bytes``, and at least 1."""
+    per_frame = int(n_rx) * int(n_rows) * int(C) * 8
+    if per_frame < 1:
+        raise ValueError(f"capon_pass_frames: n_rx {n_rx}, n_rows {n_rows} and C {C} must all be positive")
+    return max(1, int(budget_bytes) // per_frame)
+
+
+def capon_passes(n_frames: int, frames_per_pass: int):
+    """``[(f0, f1), ...]``: the frame intervals of the passes, in order; the last one may be shorter."""
+    n, step = int(n_frames), int(frames_per_pass)
+    if step < 1:
+        raise ValueError(f"frames_per_pass must be a positive integer, got {frames_per_pass}")
+    return [(f0, min(f0 + step, n)) for f0 in range(0, n, step)]
+
+
+def capon_cube_args(V: int, S: int, thetas_rad, rx_antennas, range_bins, delta, frames_per_pass):
+    """The argument checks of ``capon_range_angle`` / ``process_cube`` (no device is touched): ``(thetas float64 [T], rx list,
+    (r_lo, r_hi), delta, frames_per_pass or None)``."""
+    th = np.ascontiguousarray(thetas_rad, dtype=np.float64)
+    if th.ndim != 1 or th.size < 1:
+        raise ValueError(f"capon_range_angle: thetas_rad must be a non-empty 1-D grid of angles, got shape {th.shape}")
+    if not np.all(np.isfinite(th)):
+        raise ValueError(f"capon_range_angle: thetas_rad holds a value that is not finite ({th[~np.isfinite(th)][0]})")
+    rx_in = np.asarray(rx_antennas)
+    if rx_in.ndim != 1 or not 1 <= rx_in.size <= 16:
+        raise ValueError(f"capon_range_angle: rx_antennas must list 1..16 antennas (a uniform line array in list order), got "
+                         f"{rx_in.size} in shape {rx_in.shape}")
+    if not np.all(rx_in == np.floor(rx_in)):
+        raise ValueError(f"capon_range_angle: rx_antennas {rx_in.tolist()} are not integers")
+    rx = [int(i) for i in rx_in]
+    for i in rx:
+        if not -V <= i < V:
+            raise IndexError(f"capon_range_angle: rx_antennas index {i} is out of bounds for {V} antennas")
+    if range_bins is None:
+        range_bins = (0, S)
+    try:
+        r_lo, r_hi = (int(r) for r in range_bins)
+    except (TypeError, ValueError):
+        raise ValueError(f"capon_range_angle: range_bins must be a pair (r_lo, r_hi) of bin indices, got {range_bins!r}") from None
+    if not 0 <= r_lo < r_hi <= S:
+        raise ValueError(f"capon_range_angle: range_bins ({r_lo}, {r_hi}) is not 0 <= r_lo < r_hi <= {S}")
+    d = float(delta)
+    if not (np.isfinite(d) and d >= 0.0):
+        raise ValueError(f"capon_range_angle: delta {delta} is not a finite number >= 0")
+    if frames_per_pass is not None:
+        if int(frames_per_pass) != frames_per_pass or int(frames_per_pass) < 1:
+            raise ValueError(f"capon_range_angle: frames_per_pass must be a positive integer, got {frames_per_pass}")
+        frames_per_pass = int(frames_per_pass)
+    return th, [i % V for i in rx], (r_lo, r_hi), d, frames_per_pass
+
+
+def capon_from_cubes(ctx: _lib.Context, d_cubes: int, d_snap: _lib.DeviceBuffer, d_out: _lib.DeviceBuffer, n_frames: int, shape,
+                     thetas: np.ndarray, rx, window, delta: float, perform_windowing: bool, frames_per_pass: int) -> None:
+    """The two device stages of the Capon range-azimuth map on cubes at device address ``d_cubes`` (``[n_frames][V][S][C]``
+    complex64): per pass of ``frames_per_pass`` frames ``mmw_range_snapshots`` into ``d_snap``, then ``mmw_capon`` from there into
+    the pass's slice of ``d_out`` (float32 ``[n_frames][R_w][T]``), all on the context's queue in order -- the queue is what keeps
+    a pass's snapshots alive until its Capon launch has read them."""
+    V, S, C = shape
+    (r_lo, r_hi), T, n_rx = window, len(thetas), len(rx)
+    Rw = r_hi - r_lo
+    rx_arr, _ = _lib.int_array(rx)
+    th = thetas.ctypes.data_as(C_POINTER_DOUBLE)
+    for f0, f1 in capon_passes(n_frames, frames_per_pass):
+        _lib.check(ctx.lib.mmw_range_snapshots(ctx.handle, d_cubes + f0 * V * S * C * 8, d_snap.ptr, f1 - f0, V, S, C, rx_arr, n_rx,
+                                               r_lo, r_hi, int(bool(perform_windowing))))
+        _lib.check(ctx.lib.mmw_capon(ctx.handle, d_snap.ptr, th, d_out.at(f0 * Rw * T * 4), f1 - f0, n_rx, Rw, C, T, delta))
+
+
+C_POINTER_DOUBLE = C.POINTER(C.c_double)
+
+
 class CaponBeamformer:
     """MVDR angle spectrum per range bin on a V-element half-wavelength ULA (no upstream oracle).
 
@@ -112,4 +191,37 @@ class CaponBeamformer:
         th = self.thetas_rad.ctypes.data_as(C.POINTER(C.c_double))
         _lib.check(ctx.lib.mmw_capon(ctx.handle, d_X.ptr, th, d_out.ptr, F, V, R, K, T, self.delta))
         out = d_out.download((F, R, T), np.float32).astype(np.float64)
+        return out[0] if single else out
+
+    def process_cube(self, cube_vsc: np.ndarray, rx_antennas, range_bins=None, perform_windowing: bool = True) -> np.ndarray:
+        """One radar cube ``[V, S, C]`` (samples on the slow axis, chirps contiguous) -> float64 ``[R_w, T]``; a batch
+        ``[F, V, S, C]`` -> ``[F, R_w, T]``.  ``rx_antennas``: the 1..16 antennas of the azimuth row, a half-wavelength line
+        array in list order; ``range_bins=(r_lo, r_hi)`` in bin indices (default: the whole profile).  The cube is uploaded as
+        it is and the snapshots -- the Hann-windowed range FFT of every chirp of the listed antennas -- are made on the device
+        (``mmw_range_snapshots``) and handed to ``mmw_capon`` there, in passes of ``capon_pass_frames`` frames: the two calls
+        ``FramePipeline.capon_range_angle`` makes on resident frames."""
+        cube = np.asarray(cube_vsc)
+        single = cube.ndim == 3
+        if cube.ndim not in (3, 4):
+            raise ValueError(f"expected a [V, S, C] cube or a [F, V, S, C] batch, got shape {cube.shape}")
+        F = 1 if single else cube.shape[0]
+        V, S, Cc = cube.shape[-3:]
+        if min(V, S, Cc) < 1:
+            raise ValueError(f"expected a [V, S, C] cube or a [F, V, S, C] batch with V, S, C >= 1, got shape {cube.shape}")
+        th, rx, (r_lo, r_hi), delta, _ = capon_cube_args(V, S, self.thetas_rad, rx_antennas, range_bins, self.delta, None)
+        Rw, T = r_hi - r_lo, len(th)
+        if F == 0:
+            return np.zeros((0, Rw, T))
+        if self._ctx is None:
+            self._ctx = _lib.default_context()
+        if self._bufs is None:
+            self._bufs = _lib.BufferSet(self._ctx)
+        ctx, bufs = self._ctx, self._bufs
+        cube = np.ascontiguousarray(cube, dtype=np.complex64)
+        fpp = min(F, capon_pass_frames(len(rx), Rw, Cc))
+        d_cube, d_out = bufs.get("cap_cube", cube.nbytes), bufs.get("cap_p", F * Rw * T * 4)
+        d_snap = bufs.get("cap_snap", fpp * len(rx) * Rw * Cc * 8)
+        d_cube.upload(cube)
+        capon_from_cubes(ctx, d_cube.ptr, d_snap, d_out, F, (V, S, Cc), th, rx, (r_lo, r_hi), delta, perform_windowing, fpp)
+        out = d_out.download((F, Rw, T), np.float32).astype(np.float64)
         return out[0] if single else out
