@@ -120,7 +120,10 @@ int mmw_virtual_array_reformat_i16(mmw_ctx *ctx, const void *d_raw_i16, void *d_
  * mmw_angle_fft: d_out[F][A][S][C] c64 = fftshift_A FFT_A( zero-pad_{V->A}( hann(V) rd ) )
  *   last stage of RangeAngleProcessorDBSEnhanced.compute_3d_windowed_fft
  *   (processors/range_angle_resp_dbs_enhanced.py:175-196).  With MMW_ANGLE_MAGNITUDE the output is
- *   float32 |.| [F][A][S][C] instead (perform/process_dbs_enhanced :293).
+ *   float32 |.| [F][A][S][C] instead (perform/process_dbs_enhanced :293).  Any 1 <= V <= A <= 4096; the shift is
+ *   np.fft.fftshift's for odd A too (out[(k + A/2) mod A] = X[k]).  The window is np.hanning(V), whose end points are 0:
+ *   with V = 2 (so at A = 2 with the window on) every output is exactly zero, as the reference's would be, and with
+ *   V = 1 the window is [1]; MMW_ANGLE_NO_WINDOW is the way to a two-antenna spectrum.
  * mmw_chain3d: mmw_range_doppler followed by mmw_angle_fft, chunked so the RD intermediate
  *   stays cache-resident; d_rd may be NULL (internal scratch) or [F][V][S][C] to keep it.
  *   Replaces compute_3d_windowed_fft (:137-198) end to end. */
@@ -551,7 +554,10 @@ int mmw_diag_mfma_peak(mmw_ctx *ctx, int kind, double *tflops);
  * only): plan[0] = 0 fused 256x128 | 1 LDS-resident power of two | 2 mixed radix | 3 generic two-kernel path |
  * 4 single pass with half / three quarters of the plane carried in registers (planes of 32768 / 65536 cells);
  * for the mixed-radix kernel plan[1..7] = register class, has a run-time-radix level, S1, S2, C1, C2 (S = S1 S2,
- * C = C1 C2), dynamic LDS bytes.  float64 != 0 asks for the float64 CFAR-plane variant. */
+ * C = C1 C2), dynamic LDS bytes.  float64 != 0 asks for the float64 CFAR-plane variant: 2 or 3 by the very test
+ * mmw_range_doppler_mag64 makes (power-of-two planes under 8192 cells and planes beyond the LDS: 3; MMW_NO_MIXED_RD = 1
+ * in the environment: 3 everywhere); the fused 256 x 128 batch kernel of that entry is not reported.  The float32
+ * answer does not read the MMW_NO_*_RD switches. */
 int mmw_diag_rd_plan(int S, int C, int float64, int plan[8]);
 /* Schedule mmw_chain3d(d_rd = NULL) would use for this batch on this context (host logic + environment knobs only):
  * plan[0] = 1 overlapped (range-Doppler || angle on two queues) / 0 serial, plan[1] = frames per kernel launch,

@@ -523,6 +523,17 @@ int mmw_range_doppler(mmw_ctx *ctx, const void *d_cubes, void *d_out, void *d_ma
     return range_doppler_impl(ctx, d_cubes, d_out, d_mag_f32, n_frames, V, S, C);
 }
 
+// Does the float64 CFAR plane of an S x C shape go through the LDS-resident single-pass kernel?  Every plane that fits in
+// float64 except small power-of-two ones, where the two-kernel register-FFT path is as fast (64 x 64, 512 x 8: equal;
+// 128 x 64, 256 x 32: single pass +18 %).  One predicate for range_doppler_mag64_impl and mmw_diag_rd_plan.
+static bool rd64_takes_mixed(int S, int C, RdMixedPlan *out) {
+    RdMixedPlan mp;
+    if (is_pow2(S) && is_pow2(C) && (long)S * C < 8192) return false;
+    if (env_int("MMW_NO_MIXED_RD", 0) || !rd_mixed_plan(S, C, sizeof(cplx<double>), &mp)) return false;
+    if (out) *out = mp;
+    return true;
+}
+
 static int range_doppler_mag64_impl(mmw_ctx *ctx, const void *d_cubes, double *d_mag, int n_frames, int V, int S,
                                    int C, int rx_idx) {
     MMW_REQUIRE(ctx && d_cubes && d_mag, "null argument");
@@ -554,13 +565,9 @@ static int range_doppler_mag64_impl(mmw_ctx *ctx, const void *d_cubes, double *d
         hipLaunchKernelGGL(k_rd_mag64_256x128, dim3((unsigned)grid), dim3(C64_NT), lds, ctx->stream, ra);
         return check_launch("rd_mag64_256x128");
     }
-    RdMixedPlan mp;
-    // LDS-resident single-pass kernel for every plane that fits in float64 except small power-of-two ones, where the
-    // two-kernel register-FFT path is as fast (64 x 64, 512 x 8: equal; 128 x 64, 256 x 32: single pass +18 %)
-    if (!is_pow2(S) || !is_pow2(C) || (long)S * C >= 8192)
-        if (rd_mixed_plan(S, C, sizeof(cplx<double>), &mp) && !env_int("MMW_NO_MIXED_RD", 0))
-            return launch_rd_mixed<double, true>(ctx, (const cplx<float> *)d_cubes + (long)rx_idx * S * C,
-                                                 (long)V * S * C, d_mag, n_frames, S, C);
+    if (rd64_takes_mixed(S, C, nullptr))
+        return launch_rd_mixed<double, true>(ctx, (const cplx<float> *)d_cubes + (long)rx_idx * S * C,
+                                             (long)V * S * C, d_mag, n_frames, S, C);
     // two passes with a complex128 intermediate: chunks of frames small enough for the intermediate to stay in the
     // Infinity Cache between them (128 MB; it also bounds the scratch: all 1250 frames of the bench at once were 640 MB)
     const size_t plane_bytes = (size_t)S * C * sizeof(cplx<double>);
@@ -2729,10 +2736,9 @@ int mmw_diag_rd_plan(int S, int C, int float64, int plan[8]) {
     MMW_REQUIRE(plan && S > 0 && C > 0, "bad argument");
     for (int i = 0; i < 8; ++i) plan[i] = 0;
     RdMixedPlan pl{};
-    if (float64) {
-        const bool pow2 = is_pow2(S) && is_pow2(C);
-        plan[0] = (!pow2 && rd_mixed_plan(S, C, sizeof(cplx<double>), &pl)) ? 2 : 3;
-    } else if (fused_rd_ok(S, C))
+    if (float64)
+        plan[0] = rd64_takes_mixed(S, C, &pl) ? 2 : 3;       // (the entry's own test: MMW_NO_MIXED_RD included)
+    else if (fused_rd_ok(S, C))
         plan[0] = 0;
     else if (rd_lds_supported(S, C))
         plan[0] = 1;
