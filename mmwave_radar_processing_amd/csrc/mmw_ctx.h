@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -227,18 +228,73 @@ inline int join_pipe(mmw_ctx *ctx, bool keep_tail = false) {
 }
 #define MMW_JOIN(ctx) MMW_TRY(mmw::join_pipe(ctx))
 
+// The side queues of a context, by group: THE list of them (a new queue is added here, and nowhere else, to be waited for and
+// destroyed).  The launch code reads the members by name; whoever waits for queues or destroys them goes through these helpers.
+enum QueueGroup { Q_CHAIN = 0, Q_DETECT, Q_COPY, Q_GROUPS };
+struct QueueList {
+    hipStream_t *q[4];
+    int n;
+};
+inline QueueList queues_of(mmw_ctx *ctx, int group) {
+    switch (group) {
+        case Q_CHAIN: return {{&ctx->q_rd, &ctx->q_ang, &ctx->q_ang2}, 3};
+        case Q_DETECT: return {{&ctx->q_drd, &ctx->q_dscr, &ctx->q_side, &ctx->q_tail}, 4};
+        default: return {{&ctx->q_copy}, 1};
+    }
+}
+inline hipError_t first_error(hipError_t first, hipError_t e) { return first != hipSuccess ? first : e; }
+// Host wait for every queue of the group that exists.  It goes on after an error and returns the first one: MMW_HIP(drain(..))
+// where the caller reports it, (void)drain(..) on teardown and failure paths.
+inline hipError_t drain(mmw_ctx *ctx, int group) {
+    hipError_t first = hipSuccess;
+    const QueueList l = queues_of(ctx, group);
+    for (int i = 0; i < l.n; ++i)
+        if (*l.q[i]) first = first_error(first, hipStreamSynchronize(*l.q[i]));
+    if (group == Q_DETECT) ctx->tail_pending = false;       // a deferred tail has run: nothing is left to join (tail_pending => q_tail exists)
+    return first;
+}
+// ... for everything the context has in flight: every side queue, then the main stream
+inline hipError_t drain_all(mmw_ctx *ctx) {
+    hipError_t first = hipSuccess;
+    for (int g = 0; g < Q_GROUPS; ++g) first = first_error(first, drain(ctx, g));
+    if (ctx->stream) first = first_error(first, hipStreamSynchronize(ctx->stream));
+    return first;
+}
+inline hipError_t destroy_queues(mmw_ctx *ctx, int group) {
+    hipError_t first = drain(ctx, group);
+    const QueueList l = queues_of(ctx, group);
+    for (int i = 0; i < l.n; ++i) {
+        if (*l.q[i]) first = first_error(first, hipStreamDestroy(*l.q[i]));
+        *l.q[i] = nullptr;
+    }
+    return first;
+}
+// Queues on two complementary CU sets, for two kernels that run side by side: CU-mask bits [0, rd_cus) belong to the first
+// queue of `qs` (all null on entry), the other bits to each of the rest.  rd_cus == 0: no masks (each queue may use every CU).
+// On a failure nothing is left behind: the handles are null again and HIP's last error is cleared.
+inline hipError_t create_split_queues(mmw_ctx *ctx, int rd_cus, std::initializer_list<hipStream_t *> qs) {
+    const int words = (ctx->num_cu + 31) / 32;
+    std::vector<uint32_t> m_first(words, 0u), m_rest(words, 0u);
+    for (int i = 0; i < ctx->num_cu; ++i) ((i < rd_cus) ? m_first : m_rest)[i / 32] |= 1u << (i % 32);
+    hipError_t e = hipSuccess;
+    for (hipStream_t *q : qs) {
+        if (e != hipSuccess) break;
+        const uint32_t *m = (q == *qs.begin() ? m_first : m_rest).data();
+        e = rd_cus > 0 ? hipExtStreamCreateWithCUMask(q, (uint32_t)words, m) : hipStreamCreateWithFlags(q, hipStreamNonBlocking);
+    }
+    if (e == hipSuccess) return e;
+    for (hipStream_t *q : qs) {
+        if (*q) (void)hipStreamDestroy(*q);
+        *q = nullptr;
+    }
+    (void)hipGetLastError();
+    return e;
+}
+
 inline int ensure_scratch(mmw_ctx *ctx, size_t bytes) {
     if (ctx->scratch_bytes >= bytes) return MMW_OK;
     if (ctx->scratch) {
-        if (ctx->q_rd) {
-            MMW_HIP(hipStreamSynchronize(ctx->q_rd));
-            MMW_HIP(hipStreamSynchronize(ctx->q_ang));
-            MMW_HIP(hipStreamSynchronize(ctx->q_ang2));
-        }
-        if (ctx->q_side) MMW_HIP(hipStreamSynchronize(ctx->q_side));
-        if (ctx->q_tail) MMW_HIP(hipStreamSynchronize(ctx->q_tail));
-        ctx->tail_pending = false;
-        MMW_HIP(hipStreamSynchronize(ctx->stream));
+        MMW_HIP(drain_all(ctx));
         MMW_HIP(hipFree(ctx->scratch));
         ctx->scratch = nullptr;
         ctx->scratch_bytes = 0;

@@ -1206,8 +1206,7 @@ inline ChainSync rd_ticket_sync(unsigned *words, int n_frames, int V) {
 inline int ensure_help_sync(mmw_ctx *ctx, size_t words) {
     if (ctx->help_sync_words >= words) return MMW_OK;
     if (ctx->help_sync) {
-        if (ctx->q_tail) MMW_HIP(hipStreamSynchronize(ctx->q_tail));
-        MMW_HIP(hipStreamSynchronize(ctx->stream));
+        MMW_HIP(drain_all(ctx));
         MMW_HIP(hipFree(ctx->help_sync));
         ctx->help_sync = nullptr;
         ctx->help_sync_words = 0;

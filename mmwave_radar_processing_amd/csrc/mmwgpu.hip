@@ -176,7 +176,7 @@ int mmw_ctx_destroy(mmw_ctx *ctx) {
     if (!ctx) return MMW_OK;
     sync_slot_forget(ctx);
     (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    (void)drain_all(ctx);       // first: a deferred detection tail, chain work and copies are not joined into the main stream
     for (auto &kv : ctx->tables) (void)hipFree(kv.second);
     for (auto &pl : ctx->czt_plans) {
         (void)hipFree(pl.d_segs);
@@ -186,48 +186,18 @@ int mmw_ctx_destroy(mmw_ctx *ctx) {
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->capon_z) (void)hipFree(ctx->capon_z);
     if (ctx->chain_ctl) (void)hipFree(ctx->chain_ctl);
-    if (ctx->t0) (void)hipEventDestroy(ctx->t0);
-    if (ctx->t1) (void)hipEventDestroy(ctx->t1);
-    drain_profile(ctx);
-    for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
-    if (ctx->q_rd) {
-        (void)hipStreamSynchronize(ctx->q_rd);
-        (void)hipStreamSynchronize(ctx->q_ang);
-        (void)hipStreamSynchronize(ctx->q_ang2);
-        (void)hipStreamDestroy(ctx->q_rd);
-        (void)hipStreamDestroy(ctx->q_ang);
-        (void)hipStreamDestroy(ctx->q_ang2);
-    }
-    if (ctx->pipe_begin) {
-        for (int i = 0; i < PIPE_RING_MAX; ++i) {
-            if (ctx->pipe_rd[i]) (void)hipEventDestroy(ctx->pipe_rd[i]);
-            if (ctx->pipe_ang[i]) (void)hipEventDestroy(ctx->pipe_ang[i]);
-        }
-        (void)hipEventDestroy(ctx->pipe_begin);
-    }
-    if (ctx->q_drd) {
-        (void)hipStreamSynchronize(ctx->q_drd);
-        (void)hipStreamSynchronize(ctx->q_dscr);
-        (void)hipStreamDestroy(ctx->q_drd);
-        (void)hipStreamDestroy(ctx->q_dscr);
-    }
-    if (ctx->q_side) {
-        (void)hipStreamSynchronize(ctx->q_side);
-        (void)hipStreamDestroy(ctx->q_side);
-    }
-    if (ctx->q_tail) {
-        (void)hipStreamSynchronize(ctx->q_tail);
-        (void)hipStreamDestroy(ctx->q_tail);
-    }
     if (ctx->help_sync) (void)hipFree(ctx->help_sync);
-    for (hipEvent_t e : {ctx->det_begin, ctx->det_rd_done, ctx->det_scr_done, ctx->side_fork, ctx->side_join, ctx->tail_done,
-                         ctx->help_begin, ctx->help_done})
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->q_copy) {
-        (void)hipStreamSynchronize(ctx->q_copy);
-        (void)hipStreamDestroy(ctx->q_copy);
-    }
     for (void *p : ctx->host_owned) (void)hipHostFree(p);
+    drain_profile(ctx);
+    for (int g = 0; g < Q_GROUPS; ++g) (void)destroy_queues(ctx, g);
+    // every event of the context (a half-built one has nulls among them)
+    std::vector<hipEvent_t> events = {ctx->pipe_begin, ctx->det_begin, ctx->det_rd_done, ctx->det_scr_done, ctx->side_fork, ctx->side_join,
+                                      ctx->tail_done, ctx->help_begin, ctx->help_done, ctx->t0, ctx->t1};
+    events.insert(events.end(), ctx->pipe_rd, ctx->pipe_rd + PIPE_RING_MAX);
+    events.insert(events.end(), ctx->pipe_ang, ctx->pipe_ang + PIPE_RING_MAX);
+    events.insert(events.end(), ctx->ev_pool.begin(), ctx->ev_pool.end());
+    for (hipEvent_t e : events)
+        if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return MMW_OK;
@@ -309,7 +279,7 @@ int mmw_host_free(mmw_ctx *ctx, void *h_ptr) {
     auto it = std::find(ctx->host_owned.begin(), ctx->host_owned.end(), h_ptr);
     MMW_REQUIRE(it != ctx->host_owned.end(), "pointer was not allocated by mmw_host_alloc of this context");
     MMW_HIP(hipSetDevice(ctx->device));
-    if (ctx->q_copy) MMW_HIP(hipStreamSynchronize(ctx->q_copy));
+    MMW_HIP(drain(ctx, Q_COPY));
     MMW_HIP(hipStreamSynchronize(ctx->stream));
     MMW_HIP(hipHostFree(h_ptr));
     ctx->host_owned.erase(it);
@@ -903,15 +873,7 @@ int mmw_doppler_azimuth_zoom(mmw_ctx *ctx, const void *d_cubes, float *d_out, in
 static int ensure_pipe_queues(mmw_ctx *ctx, int rd_cus) {
     if (ctx->pipe_unavailable) return set_error(MMW_ERR_UNSUPPORTED, "chain queues unavailable on this runtime");
     if (ctx->q_rd && ctx->q_rd_cus == rd_cus) return MMW_OK;
-    if (ctx->q_rd) {
-        MMW_HIP(hipStreamSynchronize(ctx->q_rd));
-        MMW_HIP(hipStreamSynchronize(ctx->q_ang));
-        MMW_HIP(hipStreamSynchronize(ctx->q_ang2));
-        MMW_HIP(hipStreamDestroy(ctx->q_rd));
-        MMW_HIP(hipStreamDestroy(ctx->q_ang));
-        MMW_HIP(hipStreamDestroy(ctx->q_ang2));
-        ctx->q_rd = ctx->q_ang = ctx->q_ang2 = nullptr;
-    }
+    MMW_HIP(destroy_queues(ctx, Q_CHAIN));
     if (!ctx->pipe_begin) {                         // events are created once per context
         for (int i = 0; i < PIPE_RING_MAX; ++i) {
             MMW_HIP(hipEventCreateWithFlags(&ctx->pipe_rd[i], hipEventDisableTiming));
@@ -921,27 +883,10 @@ static int ensure_pipe_queues(mmw_ctx *ctx, int rd_cus) {
     }
     // Two angle queues on the same CUs take alternate chunks: the barrier / marker packets around one launch are
     // processed while the other queue's kernel runs (one queue alone idles ~15 us per launch).
-    hipError_t e1, e2 = hipSuccess, e3 = hipSuccess;
-    if (rd_cus > 0) {
-        const int words = (ctx->num_cu + 31) / 32;
-        std::vector<uint32_t> m_rd(words, 0u), m_ang(words, 0u);
-        for (int i = 0; i < ctx->num_cu; ++i) ((i < rd_cus) ? m_rd : m_ang)[i / 32] |= 1u << (i % 32);
-        e1 = hipExtStreamCreateWithCUMask(&ctx->q_rd, (uint32_t)words, m_rd.data());
-        if (e1 == hipSuccess) e2 = hipExtStreamCreateWithCUMask(&ctx->q_ang, (uint32_t)words, m_ang.data());
-        if (e1 == hipSuccess && e2 == hipSuccess) e3 = hipExtStreamCreateWithCUMask(&ctx->q_ang2, (uint32_t)words, m_ang.data());
-    } else {
-        e1 = hipStreamCreateWithFlags(&ctx->q_rd, hipStreamNonBlocking);
-        if (e1 == hipSuccess) e2 = hipStreamCreateWithFlags(&ctx->q_ang, hipStreamNonBlocking);
-        if (e1 == hipSuccess && e2 == hipSuccess) e3 = hipStreamCreateWithFlags(&ctx->q_ang2, hipStreamNonBlocking);
-    }
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
-        if (ctx->q_rd) (void)hipStreamDestroy(ctx->q_rd);
-        if (ctx->q_ang) (void)hipStreamDestroy(ctx->q_ang);
-        ctx->q_rd = ctx->q_ang = ctx->q_ang2 = nullptr;
+    const hipError_t e = create_split_queues(ctx, rd_cus, {&ctx->q_rd, &ctx->q_ang, &ctx->q_ang2});
+    if (e != hipSuccess) {
         ctx->pipe_unavailable = true;
-        (void)hipGetLastError();
-        return set_error(MMW_ERR_UNSUPPORTED, "chain queue creation failed: %s",
-                         hipGetErrorString(e1 != hipSuccess ? e1 : (e2 != hipSuccess ? e2 : e3)));
+        return set_error(MMW_ERR_UNSUPPORTED, "chain queue creation failed: %s", hipGetErrorString(e));
     }
     ctx->q_rd_cus = rd_cus;
     for (int i = 0; i < PIPE_RING_MAX; ++i) ctx->pipe_ang_used[i] = false;   // the old queues were drained above
@@ -1098,7 +1043,7 @@ int chain_settle(mmw_ctx *ctx) {
         mmw_ctx *c;
         ~Done() { c->chain_settling = false; }
     } done{ctx};
-    if (ctx->q_rd) {
+    if (ctx->q_rd) {        // the two queues of the device-synchronised calls only (q_ang2 may hold an event-mode call: not waited for)
         MMW_HIP(hipStreamSynchronize(ctx->q_rd));
         MMW_HIP(hipStreamSynchronize(ctx->q_ang));
     }
@@ -1154,9 +1099,7 @@ static int chain3d_sync(mmw_ctx *ctx, const ChainPlan &plan, const void *d_cubes
     const long layout[6] = {V, bins, plan.vskip, plan.ring_frames, tiles, (long)(uintptr_t)ctx->scratch};
     if (std::memcmp(layout, ctx->chain_layout, sizeof(layout)) != 0) {
         // new ring layout: nothing of the old one may be in flight, counters restart from zero
-        MMW_HIP(hipStreamSynchronize(ctx->q_rd));
-        MMW_HIP(hipStreamSynchronize(ctx->q_ang));
-        MMW_HIP(hipStreamSynchronize(ctx->q_ang2));
+        MMW_HIP(drain(ctx, Q_CHAIN));
         MMW_HIP(hipMemsetAsync(ctx->chain_ctl, 0, CTL_WORDS * sizeof(unsigned), ctx->stream));
         MMW_HIP(hipStreamSynchronize(ctx->stream));
         std::memcpy(ctx->chain_layout, layout, sizeof(layout));
@@ -1237,7 +1180,7 @@ static int chain3d_sync(mmw_ctx *ctx, const ChainPlan &plan, const void *d_cubes
         }
     }
     if (rc != MMW_OK) {
-        // a launch failed: the counters no longer match the host mirror; drain and force a fresh layout next time
+        // a launch failed: the counters no longer match the host mirror; drain (the two queues this call used) and force a fresh layout next time
         (void)sync_slot_launched(ctx, false);
         (void)hipStreamSynchronize(ctx->q_rd);
         (void)hipStreamSynchronize(ctx->q_ang);
@@ -1314,9 +1257,7 @@ static int chain3d_impl(mmw_ctx *ctx, const void *d_cubes, RawView rv, void *d_r
     auto fail = [&](int rc) {           // leave nothing in flight that join_pipe's events do not cover
         ctx->stream = main_stream;
         ctx->active_cus = 0;
-        (void)hipStreamSynchronize(ctx->q_rd);
-        (void)hipStreamSynchronize(ctx->q_ang);
-        (void)hipStreamSynchronize(ctx->q_ang2);
+        (void)drain(ctx, Q_CHAIN);
         return rc;
     };
 #define MMW_PIPE_HIP(call)                                                                                        \
@@ -2107,32 +2048,20 @@ int mmw_angle_argmax_exact(mmw_ctx *ctx, const void *d_cubes, const float *d_l1,
 // The two queues of the overlapped detection schedule: the range-Doppler producer owns the first rd_cus CU-mask bits, the
 // screening consumer the rest (mask bit i belongs to XCD i % 8, and to that XCD's shader engines in turn: multiples of 32
 // keep every engine of every XCD equally populated -- an engine with fewer CUs than its neighbours paces the whole launch).
+// A new split drains and destroys the whole detection group (a pending tail included); detect_tail makes its two queues again.
 static int ensure_det_queues(mmw_ctx *ctx, int rd_cus) {
     if (ctx->det_unavailable) return set_error(MMW_ERR_UNSUPPORTED, "detection queues unavailable on this runtime");
     if (ctx->q_drd && ctx->q_drd_cus == rd_cus) return MMW_OK;
-    if (ctx->q_drd) {
-        MMW_HIP(hipStreamSynchronize(ctx->q_drd));
-        MMW_HIP(hipStreamSynchronize(ctx->q_dscr));
-        MMW_HIP(hipStreamDestroy(ctx->q_drd));
-        MMW_HIP(hipStreamDestroy(ctx->q_dscr));
-        ctx->q_drd = ctx->q_dscr = nullptr;
-    }
+    MMW_HIP(destroy_queues(ctx, Q_DETECT));
     if (!ctx->det_begin) {
         MMW_HIP(hipEventCreateWithFlags(&ctx->det_begin, hipEventDisableTiming));
         MMW_HIP(hipEventCreateWithFlags(&ctx->det_rd_done, hipEventDisableTiming));
         MMW_HIP(hipEventCreateWithFlags(&ctx->det_scr_done, hipEventDisableTiming));
     }
-    const int words = (ctx->num_cu + 31) / 32;
-    std::vector<uint32_t> m_rd(words, 0u), m_scr(words, 0u);
-    for (int i = 0; i < ctx->num_cu; ++i) ((i < rd_cus) ? m_rd : m_scr)[i / 32] |= 1u << (i % 32);
-    hipError_t e1 = hipExtStreamCreateWithCUMask(&ctx->q_drd, (uint32_t)words, m_rd.data()), e2 = hipSuccess;
-    if (e1 == hipSuccess) e2 = hipExtStreamCreateWithCUMask(&ctx->q_dscr, (uint32_t)words, m_scr.data());
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        if (ctx->q_drd) (void)hipStreamDestroy(ctx->q_drd);
-        ctx->q_drd = ctx->q_dscr = nullptr;
+    const hipError_t e = create_split_queues(ctx, rd_cus, {&ctx->q_drd, &ctx->q_dscr});
+    if (e != hipSuccess) {
         ctx->det_unavailable = true;
-        (void)hipGetLastError();
-        return set_error(MMW_ERR_UNSUPPORTED, "detection queue creation failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+        return set_error(MMW_ERR_UNSUPPORTED, "detection queue creation failed: %s", hipGetErrorString(e));
     }
     ctx->q_drd_cus = rd_cus;
     return MMW_OK;
@@ -2556,12 +2485,11 @@ int detect_tail_end(DetectCall &d, bool join_now) {
 // speculative slots --, then k_detect_insert puts the cells decided positive into their lists.
 int detect_tail(DetectCall &d, bool want_stats) {
     mmw_ctx *ctx = d.ctx;
-    if (!ctx->q_side) {
-        MMW_HIP(hipStreamCreateWithFlags(&ctx->q_side, hipStreamNonBlocking));
-        MMW_HIP(hipStreamCreateWithFlags(&ctx->q_tail, hipStreamNonBlocking));
-        for (hipEvent_t *e : {&ctx->side_fork, &ctx->side_join, &ctx->tail_done, &ctx->help_begin, &ctx->help_done})
-            MMW_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    }
+    // (each handle on its own: ensure_det_queues destroys the whole detection group when the CU split changes, the events stay)
+    for (hipStream_t *q : {&ctx->q_side, &ctx->q_tail})
+        if (!*q) MMW_HIP(hipStreamCreateWithFlags(q, hipStreamNonBlocking));
+    for (hipEvent_t *e : {&ctx->side_fork, &ctx->side_join, &ctx->tail_done, &ctx->help_begin, &ctx->help_done})
+        if (!*e) MMW_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     MMW_HIP(hipEventRecord(ctx->side_fork, ctx->stream));
     MMW_HIP(hipStreamWaitEvent(ctx->q_tail, ctx->side_fork, 0));
     // from here on the context stream is only the point the tail is joined to: on error, or when the caller wants the
@@ -2601,9 +2529,9 @@ int mmw_detect_points_supported(int S, int C, int cfar_kind, int train_r, int tr
 
 // Invariants of every return path:
 //  1. ctx->stream is the context's main stream (the stages switch it with StreamScope only);
-//  2. everything enqueued on q_side, q_tail, q_drd, q_dscr is ordered before the main stream or registered as the pending tail with
-//     its buffer list (detect_tail_end).  The stages' own joins "in any case" cover a failed launch; a failed HIP call between a
-//     launch and its join is covered by ONE mechanism, the host wait for all four queues at the end of the driver, not by the guards;
+//  2. everything enqueued on the detection group (q_drd, q_dscr, q_side, q_tail) is ordered before the main stream or registered as
+//     the pending tail with its buffer list (detect_tail_end).  The stages' own joins "in any case" cover a failed launch; a failed HIP
+//     call between a launch and its join is covered by ONE mechanism, drain(ctx, Q_DETECT) at the end of the driver, not by the guards;
 //  3. no device allocation made by the call outlives it (the diagnostics' buffers are PhaseClocks; the rest belongs to the context).
 int mmw_detect_points(mmw_ctx *ctx, const void *d_cubes, void *d_rd, float *d_l1, float *d_mag32, int32_t *d_dets,
                       int32_t *d_counts, int32_t *d_az_idx, int32_t *d_el_idx, int n_frames, int V, int S, int C, int cfar_kind,
@@ -2627,9 +2555,7 @@ int mmw_detect_points(mmw_ctx *ctx, const void *d_cubes, void *d_rd, float *d_l1
     if (rc == MMW_OK) rc = d.overlap ? detect_screen_overlapped(d) : detect_screen_serial(d);
     if (rc == MMW_OK) rc = detect_tail(d, h_stats != nullptr);
     if (rc == MMW_OK && h_stats) rc = detect_read_stats(d, h_stats);
-    if (rc != MMW_OK)       // invariant 2 on every failure path (also waits for a previous call's pending tail: errors only)
-        for (hipStream_t q : {ctx->q_drd, ctx->q_dscr, ctx->q_side, ctx->q_tail})
-            if (q) (void)hipStreamSynchronize(q);
+    if (rc != MMW_OK) (void)drain(ctx, Q_DETECT);       // invariant 2 on every failure path (also waits for a previous call's pending tail: errors only)
     return rc;
 }
 
