@@ -205,7 +205,7 @@ template <typename T> int get_table(mmw_ctx *ctx, int kind, int N, const void **
 // Order the context stream after any overlapped-chain work still running on the two chain queues.  The
 // chain does not do this itself so that back-to-back mmw_chain3d calls keep the RD || angle pipeline full;
 // every other entry point that touches the context stream calls it first.
-int chain_settle(mmw_ctx *ctx);     // mmwgpu.hip
+int chain_settle(mmw_ctx *ctx);     // mmw_tu_chain.hip
 inline int join_tail(mmw_ctx *ctx) {
     if (ctx->tail_pending) {
         MMW_HIP(hipStreamWaitEvent(ctx->stream, ctx->tail_done, 0));

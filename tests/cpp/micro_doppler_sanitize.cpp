@@ -10,7 +10,7 @@
 #include "../../mmwave_radar_processing_amd/csrc/mmw_ctx.h"
 
 namespace mmw {
-int chain_settle(mmw_ctx *) { return MMW_OK; }      // mmwgpu.hip's; only reached through a context with chain work pending
+int chain_settle(mmw_ctx *) { return MMW_OK; }      // mmw_tu_chain.hip's; only reached through a context with chain work pending
 }  // namespace mmw
 
 static int fails = 0, calls = 0;

@@ -13,7 +13,7 @@
 #include "../../mmwave_radar_processing_amd/csrc/mmw_fft_generic.h"
 
 namespace mmw {
-int chain_settle(mmw_ctx *) { return MMW_OK; }      // mmwgpu.hip's; only reached through a context with chain work pending
+int chain_settle(mmw_ctx *) { return MMW_OK; }      // mmw_tu_chain.hip's; only reached through a context with chain work pending
 template <> int launch_fft_axis<float, float>(mmw_ctx *, FftArgs, int, bool) { return MMW_ERR_HIP; }    // mmw_tu_generic.hip's; never reached
 }  // namespace mmw
 

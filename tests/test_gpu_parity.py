@@ -1496,7 +1496,7 @@ def test_split_range_doppler_kernel_for_planes_beyond_the_lds(S, C, monkeypatch)
 def test_two_contexts_on_one_device_share_the_synchronised_chain(acquire_sleep_ms, monkeypatch):
     """Two contexts of one process on the SAME device, each driving large batches through mmw_chain3d from its own thread.
     Only one context at a time may keep the two persistent kernels of the device-synchronised schedule resident
-    (sync_slot_acquire in mmwgpu.hip); the other takes the event schedule for that call.  Both must finish without the
+    (sync_slot_acquire in mmw_tu_chain.hip); the other takes the event schedule for that call.  Both must finish without the
     hand-off timing out and produce the single-context result.  Second case: a sleep between a context's acquire and its
     launches (test hook) -- the other thread arrives inside that window and must still be turned away (the slot
     used to look free until the owner had recorded its events); no call may have needed the timeout re-run."""
