@@ -208,6 +208,32 @@ int mmw_micro_doppler(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_fra
 int mmw_synth_array(mmw_ctx *ctx, const void *d_cubes, int n_resident, int V, int S, int C, int v, int k, int H,
                     const int32_t *h_frames, int n_out, const double *h_P, const double *h_dirs, int T, double lambda_m, void *d_out);
 int mmw_diag_synth_array_window(int C, int k, int H, int frame, int e0, int n, int32_t *h_segs, int cap, int32_t info[4]);
+/* mmw_synth_array_calibrate: mmw_synth_array followed by n_iters rounds of self-calibration against targets of opportunity and a
+ *   contraction with the corrected geometry (mmw_synth_calib.h), all enqueued without a host synchronisation.
+ *   Arguments as mmw_synth_array with T = n_az n_el directions laid out [3][n_az][n_el]; picks use elevation index 0.
+ *   d_out [n_out][S][T] c64: the last image computed for every frame; d_Pcal [n_out][3][E] f64: the calibrated geometry (the
+ *   uncalibrated one where the loop stopped for lack of three targets, and for flagged frames); d_status [n_out] int32: the
+ *   iterations that applied a correction (0 .. n_iters), or -1: a decision fell inside the rounding band of its inputs, a phase
+ *   step lies within its error of +-pi, or the 3 x 2 system has a condition number above 1e6 -- the caller calibrates that frame on
+ *   the host; d_targets [n_out][3][2] int32: (range row, azimuth bin) of the last iteration that found three targets; -1 where none did, and for every flagged frame.
+ *   Unlike the reference (IndexError), fewer than three range peaks, and a non-finite avg (a window slot before the buffer is
+ *   all zeros: log10(0)), count as "no suitable targets": status 0.
+ *   MMW_ERR_INVALID (nothing enqueued, outputs untouched): what mmw_synth_array refuses, a null output, n_iters outside [1, 8],
+ *   n_az or n_el < 1 or n_az n_el beyond int32.  MMW_ERR_UNSUPPORTED: S > 3584 (avg and its error bound live in the LDS).  n_out == 0: MMW_OK.
+ *   Option MMW_SYNTH_CALIB_FLAG_ALL=1 flags every frame.  Profile family "synth_calib" (inside it: "synth_calib_spectra",
+ *   "synth_calib_frame", and the contractions as "synth_array").
+ * mmw_diag_synth_array_calib_host: steps 3-6 of one window on host pointers (no device, no context), the decision and solve code of
+ *   the kernels: h_avg [S] with error bounds h_avg_err [S] (null: exact), h_mag [S][n_az] image magnitudes at elevation 0 known to
+ *   +-mag_band, h_Fq [S][E] complex128 (the three picked rows are read), h_l1 [E] L1 norms of the columns for the phase error bound
+ *   (null: exact), h_P [3][E], h_dirs [3][n_az n_el] -> h_Pcal [3][E], h_targets [3][2], info = {1 applied / 0 no suitable targets /
+ *   -1 flagged, reasons (1 range, 2 azimuth, 4 phase wrap, 8 condition), 3 when three range peaks were found, condition > 1e6}.
+ *   An ill-conditioned system is flagged and still solved (minimum norm). */
+int mmw_synth_array_calibrate(mmw_ctx *ctx, const void *d_cubes, int n_resident, int V, int S, int C, int v, int k, int H,
+                              const int32_t *h_frames, int n_out, const double *h_P, const double *h_dirs, int n_az, int n_el,
+                              double lambda_m, int n_iters, void *d_out, double *d_Pcal, int32_t *d_status, int32_t *d_targets);
+int mmw_diag_synth_array_calib_host(const double *h_avg, const double *h_avg_err, int S, const double *h_mag, double mag_band, int n_az,
+                                    int n_el, const double *h_Fq, const double *h_l1, int E, const double *h_P, const double *h_dirs,
+                                    double lambda_m, double *h_Pcal, int32_t *h_targets, int32_t info[4]);
 /* mmw_mean_over_range: d_out[F][C][A] float32 = mean over range rows [s_lo, s_hi) of d_mag[F][A][S][C];
  *   with mmw_chain3d(flags | MAGNITUDE) this is DopplerAzimuthProcessor.process, coarse path
  *   (processors/doppler_azimuth_resp.py:84-128,296-334,419-491): range FFT -> range-window mask ->

@@ -838,29 +838,11 @@ class FramePipeline:
         """``(frames, buffer)``: the images of ``synthetic_array`` left in HBM, complex64 ``[n_valid][S][n_az * n_el]``, nothing
         downloaded."""
         # every argument check comes before the first use of self.ctx / self.bufs
-        if getattr(proc, "enable_calibration", False):
-            raise ValueError("synthetic_array: array calibration is not part of this build")
-        cm = proc.config_manager
-        num_tx = int(cm.frameCfg_end_index) - int(cm.frameCfg_start_index) + 1
-        if self.V % num_tx or self.S != proc.num_range_bins or self.C * num_tx != proc.chirps_per_frame:
-            raise ValueError(f"synthetic_array: cubes [{self.V}, {self.S}, {self.C}] do not match the processor's configuration "
-                             f"({num_tx} transmitters, {proc.num_range_bins} samples, {proc.chirps_per_frame} chirps per frame)")
-        num_rx = self.V // num_tx
-        rx, tx = int(proc.receiver_idx), int(proc.chirp_cfg_idx) - int(cm.frameCfg_start_index)
-        if not (0 <= rx < num_rx and 0 <= tx < num_tx):
-            raise ValueError(f"synthetic_array: receiver {rx} / chirp configuration {proc.chirp_cfg_idx} is not one of {num_rx} "
-                             f"receivers x {num_tx} transmitters")
-        vel = np.asarray(velocities, dtype=np.float64)
-        if vel.shape != (self.n_frames, 3):
-            raise ValueError(f"synthetic_array: velocities must be [{self.n_frames}, 3] (one row per resident frame), got {vel.shape}")
-        valid, P = synthetic_array_geometry(proc, vel)
-        frames = np.flatnonzero(valid).astype(np.int32)
-        dirs = np.ascontiguousarray(np.asarray(proc.d, dtype=np.float64).reshape(3, -1))
+        v, frames, P, dirs, _, _ = self._synthetic_array_arguments(proc, velocities, "synthetic_array")
         T, H, k = dirs.shape[1], int(proc.num_frames), int(proc.stride)
-        P = np.ascontiguousarray(P)
         self.d_synth = self.bufs.get("synth_array", max(len(frames), 1) * self.S * T * 8)
         dp = ctypes.POINTER(ctypes.c_double)
-        _lib.check(self.ctx.lib.mmw_synth_array(self.ctx.handle, self.d_in.ptr, self.n_frames, self.V, self.S, self.C, tx * num_rx + rx,
+        _lib.check(self.ctx.lib.mmw_synth_array(self.ctx.handle, self.d_in.ptr, self.n_frames, self.V, self.S, self.C, v,
                                                 k, H, frames.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(frames),
                                                 P.ctypes.data_as(dp), dirs.ctypes.data_as(dp), T, float(proc.lambda_m),
                                                 self.d_synth.ptr))
@@ -877,6 +859,124 @@ class FramePipeline:
         Out of scope: carrying the ``num_frames - 1`` frames of history across ``stream()`` chunks or calls (every call starts
         from a reset history), and ``MultiDeviceFramePipeline`` (a shard needs a halo of ``num_frames - 1`` frames)."""
         frames, d = self.synthetic_array_device(proc, velocities)
+        n_az, n_el = np.shape(proc.d)[1:]
+        out = d.download((len(frames), self.S, n_az * n_el), np.complex64) if len(frames) else np.zeros((0, self.S, n_az * n_el), np.complex64)
+        return frames, out.astype(np.complex128).reshape(len(frames), self.S, n_az, n_el)
+
+    def _synthetic_array_arguments(self, proc, velocities, what: str):
+        """The argument checks of ``synthetic_array*`` (no device use) -> ``(v, frames, P, dirs, n_az, n_el)``."""
+        if getattr(proc, "enable_calibration", False):
+            raise ValueError(f"{what}: array calibration is not part of this build")
+        cm = proc.config_manager
+        num_tx = int(cm.frameCfg_end_index) - int(cm.frameCfg_start_index) + 1
+        if self.V % num_tx or self.S != proc.num_range_bins or self.C * num_tx != proc.chirps_per_frame:
+            raise ValueError(f"{what}: cubes [{self.V}, {self.S}, {self.C}] do not match the processor's configuration "
+                             f"({num_tx} transmitters, {proc.num_range_bins} samples, {proc.chirps_per_frame} chirps per frame)")
+        num_rx = self.V // num_tx
+        rx, tx = int(proc.receiver_idx), int(proc.chirp_cfg_idx) - int(cm.frameCfg_start_index)
+        if not (0 <= rx < num_rx and 0 <= tx < num_tx):
+            raise ValueError(f"{what}: receiver {rx} / chirp configuration {proc.chirp_cfg_idx} is not one of {num_rx} "
+                             f"receivers x {num_tx} transmitters")
+        vel = np.asarray(velocities, dtype=np.float64)
+        if vel.shape != (self.n_frames, 3):
+            raise ValueError(f"{what}: velocities must be [{self.n_frames}, 3] (one row per resident frame), got {vel.shape}")
+        valid, P = synthetic_array_geometry(proc, vel)
+        frames = np.flatnonzero(valid).astype(np.int32)
+        n_az, n_el = (int(n) for n in np.shape(proc.d)[1:])
+        dirs = np.ascontiguousarray(np.asarray(proc.d, dtype=np.float64).reshape(3, -1))
+        return tx * num_rx + rx, frames, np.ascontiguousarray(P), dirs, n_az, n_el
+
+    def synthetic_array_calibrated_device(self, proc, velocities, num_calibration_iters: int = 1) -> Tuple[np.ndarray, _lib.DeviceBuffer]:
+        """``(frames, buffer)``: the images of ``synthetic_array_calibrated`` left in HBM, complex64 ``[n_valid][S][n_az * n_el]``.
+        Kept on the pipeline: ``synth_geometry_calibrated [n_valid, 3, E]``, ``synth_calib_status [n_valid]`` (iterations that
+        applied a correction), ``synth_calib_targets [n_valid, 3, 2]`` (range row, azimuth bin; -1: none) and ``n_flagged``."""
+        # every argument check comes before the first use of self.ctx / self.bufs
+        n_it = int(num_calibration_iters)
+        if not 1 <= n_it <= 8:
+            raise ValueError(f"synthetic_array_calibrated: num_calibration_iters {num_calibration_iters} is not in [1, 8]")
+        v, frames, P, dirs, n_az, n_el = self._synthetic_array_arguments(proc, velocities, "synthetic_array_calibrated")
+        T, H, k, n = n_az * n_el, int(proc.num_frames), int(proc.stride), len(frames)
+        E, lam = P.shape[2], float(proc.lambda_m)
+        self.d_synth = self.bufs.get("synth_array", max(n, 1) * self.S * T * 8)
+        d_P = self.bufs.get("synth_calib_P", max(n, 1) * 3 * E * 8)
+        d_st = self.bufs.get("synth_calib_status", max(n, 1) * 4)
+        d_tg = self.bufs.get("synth_calib_targets", max(n, 1) * 24)
+        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+        lib, h = self.ctx.lib, self.ctx.handle
+        _lib.check(lib.mmw_synth_array_calibrate(h, self.d_in.ptr, self.n_frames, self.V, self.S, self.C, v, k, H,
+                                                 frames.ctypes.data_as(ip), n, P.ctypes.data_as(dp), dirs.ctypes.data_as(dp), n_az, n_el,
+                                                 lam, n_it, self.d_synth.ptr, d_P.ptr, d_st.ptr, d_tg.ptr))
+        if n:
+            Pcal, status = d_P.download((n, 3, E), np.float64), d_st.download((n,), np.int32)
+            targets = d_tg.download((n, 3, 2), np.int32)
+        else:
+            Pcal, status, targets = np.zeros((0, 3, E)), np.zeros(0, np.int32), np.zeros((0, 3, 2), np.int32)
+        flagged = np.flatnonzero(status < 0)
+        self.n_flagged = len(flagged)
+        if len(flagged):
+            # the host route: calibrate_window per flagged frame, its contractions as ONE mmw_synth_array call per round over the
+            # frames still in the loop (scratch buffer), then one call with the final geometries into the frames' own slots
+            fl_frames = np.ascontiguousarray(frames[flagged])
+            d_tmp = self.bufs.get("synth_calib_flagged", len(flagged) * self.S * T * 8)
+
+            def contract_all(geoms):
+                g = np.ascontiguousarray(geoms)
+                _lib.check(lib.mmw_synth_array(h, self.d_in.ptr, self.n_frames, self.V, self.S, self.C, v, k, H,
+                                               fl_frames.ctypes.data_as(ip), len(fl_frames), g.ctypes.data_as(dp),
+                                               dirs.ctypes.data_as(dp), T, lam, d_tmp.ptr))
+                out = d_tmp.download((len(fl_frames), self.S, T), np.complex64)
+                return out.astype(np.complex128).reshape(len(fl_frames), self.S, n_az, n_el)
+
+            Cv, slab = E // H, self.S * self.C * 8
+            windows = []
+            for f in fl_frames:
+                w = np.zeros((H, self.S, Cv), dtype=complex)
+                for hh in range(H):
+                    fr = int(f) - H + 1 + hh
+                    if fr >= 0:
+                        w[hh] = self.d_in.download((self.S, self.C), np.complex64, byte_offset=(fr * self.V + v) * slab)[:, ::k]
+                windows.append(w.transpose(1, 0, 2).reshape(self.S, E))
+            geoms = P[flagged].copy()                # geometry of the latest image of every flagged frame
+            imgs = contract_all(geoms)
+            state = [dict(status=0, targets=[], Pcal=P[q].copy(), live=True) for q in flagged]
+            from .processors.synthetic_array_beamformer import calibration_spectra, calibration_targets, calibrated_geometry
+            spectra = [calibration_spectra(w) for w in windows]
+            for _ in range(n_it):
+                moved = False
+                for j, q in enumerate(flagged):
+                    st = state[j]
+                    if not st["live"]:
+                        continue
+                    tg = calibration_targets(spectra[j], imgs[j])
+                    if len(tg) < 3:
+                        st["live"], st["Pcal"] = False, P[q].copy()
+                        continue
+                    st["Pcal"] = calibrated_geometry(spectra[j], P[q], tg, np.asarray(proc.d, dtype=np.float64), lam)
+                    geoms[j], st["targets"], st["status"], moved = st["Pcal"], tg, st["status"] + 1, True
+                if not moved:
+                    break
+                imgs = contract_all(geoms)
+            for j, q in enumerate(flagged):
+                Pcal[q], status[q] = state[j]["Pcal"], state[j]["status"]
+                targets[q] = -1
+                for t, rc in enumerate(state[j]["targets"]):
+                    targets[q, t] = rc
+            # the final images of the flagged frames, into their slots of the result
+            out = d_tmp.download((len(fl_frames), self.S, T), np.complex64)
+            for j, q in enumerate(flagged):
+                self.d_synth.upload(out[j], byte_offset=int(q) * self.S * T * 8)
+        self.synth_geometry_calibrated, self.synth_calib_status, self.synth_calib_targets = Pcal, status, targets
+        return frames.astype(np.int64), self.d_synth
+
+    def synthetic_array_calibrated(self, proc, velocities, num_calibration_iters: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """``(frames, responses)``: what a fresh ``SelfCalibratingSyntheticArrayProcessor`` configured like ``proc`` (a plain
+        ``SyntheticArrayBeamformerProcessor``, only read) returns for the valid resident frames: complex128 ``[n_valid, S, n_az,
+        n_el]``.  One ``mmw_synth_array_calibrate`` call: uncalibrated images, the calibration loop and the calibrated images are
+        enqueued together; frames whose discrete decisions the device cannot take for certain (``n_flagged`` of them) are
+        calibrated on the host from their downloaded windows and contracted again.  Fewer than three range peaks or a window
+        slot before the buffer give "no suitable targets" (status 0) where the reference raises ``IndexError``.  Scope as
+        ``synthetic_array``: no history across ``stream()`` chunks, no ``MultiDeviceFramePipeline``."""
+        frames, d = self.synthetic_array_calibrated_device(proc, velocities, num_calibration_iters)
         n_az, n_el = np.shape(proc.d)[1:]
         out = d.download((len(frames), self.S, n_az * n_el), np.complex64) if len(frames) else np.zeros((0, self.S, n_az * n_el), np.complex64)
         return frames, out.astype(np.complex128).reshape(len(frames), self.S, n_az, n_el)

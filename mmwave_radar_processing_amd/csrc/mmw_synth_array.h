@@ -94,10 +94,13 @@ inline size_t sa_head_bytes(int n_out, int E, int T) {
     return (b + 255) & ~(size_t)255;
 }
 
-inline int synth_array(mmw_ctx *ctx, const void *d_cubes, int V, int S, int C, int v, int k, int H, const int *h_frames, int n_out,
-                       const double *h_P, const double *h_dirs, int T, double lambda_m, void *d_out) {
-    const int Cv = sa_cv(C, k), E = H * Cv;
-    const size_t head = sa_head_bytes(n_out, E, T);
+// Stages P, dirs and the frame list at the head of the scratch, whose first `head` bytes (>= sa_head_bytes) the caller owns.
+struct SaStaged {
+    double *d_P, *d_dirs;
+    int *d_frames;
+};
+inline int sa_stage(mmw_ctx *ctx, int S, int E, int T, const int *h_frames, int n_out, const double *h_P, const double *h_dirs,
+                    size_t head, SaStaged *st) {
     MMW_TRY(ensure_scratch(ctx, head + bartlett_plan(ctx, n_out, S, E, T).bytes));
     double *d_P = (double *)ctx->scratch, *d_dirs = d_P + (size_t)n_out * 3 * E;
     int *d_frames = (int *)(d_dirs + (size_t)3 * T);
@@ -105,8 +108,50 @@ inline int synth_array(mmw_ctx *ctx, const void *d_cubes, int V, int S, int C, i
     MMW_HIP(hipMemcpyAsync(d_P, h_P, (size_t)n_out * 3 * E * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     MMW_HIP(hipMemcpyAsync(d_dirs, h_dirs, (size_t)3 * T * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     MMW_HIP(hipMemcpyAsync(d_frames, h_frames, (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    *st = SaStaged{d_P, d_dirs, d_frames};
+    return MMW_OK;
+}
+
+// The contraction with every table already in device memory: d_P [n_out][3][E] may be the staged table or any other.
+inline int synth_array_on(mmw_ctx *ctx, const char *family, const void *d_cubes, int V, int S, int C, int v, int k, int H,
+                          const int *d_frames, int n_out, const double *d_P, const double *d_dirs, int T, double lambda_m, void *d_out,
+                          size_t head) {
+    const int Cv = sa_cv(C, k), E = H * Cv;
     const AWindow ap{d_frames, v, S, C, k, H, Cv, (long)V * S * C, ((size_t)d_cubes & 15) == 0};
-    return bartlett_on(ctx, ap, "synth_array", d_cubes, d_P, d_dirs, d_out, n_out, S, E, T, lambda_m, head);
+    return bartlett_on(ctx, ap, family, d_cubes, d_P, d_dirs, d_out, n_out, S, E, T, lambda_m, head);
+}
+
+inline int synth_array(mmw_ctx *ctx, const void *d_cubes, int V, int S, int C, int v, int k, int H, const int *h_frames, int n_out,
+                       const double *h_P, const double *h_dirs, int T, double lambda_m, void *d_out) {
+    const int E = H * sa_cv(C, k);
+    const size_t head = sa_head_bytes(n_out, E, T);
+    SaStaged st;
+    MMW_TRY(sa_stage(ctx, S, E, T, h_frames, n_out, h_P, h_dirs, head, &st));
+    return synth_array_on(ctx, "synth_array", d_cubes, V, S, C, v, k, H, st.d_frames, n_out, st.d_P, st.d_dirs, T, lambda_m, d_out, head);
+}
+
+// Every argument of mmw_synth_array is judged here, before the context is touched: the function is not given the context, so a
+// refused call cannot enqueue anything and needs no device (tests/cpp/synth_array_sanitize.cpp relies on it).
+inline int sa_validate(bool have_ctx, const void *d_cubes, int n_resident, int V, int S, int C, int v, int k, int H, const int *h_frames,
+                       int n_out, const double *h_P, const double *h_dirs, int T, double lambda_m, const void *d_out) {
+    MMW_REQUIRE(have_ctx && d_cubes && h_frames && h_P && h_dirs && d_out,
+                "null argument (ctx %d, d_cubes %d, h_frames %d, h_P %d, h_dirs %d, d_out %d)", (int)have_ctx, d_cubes != nullptr,
+                h_frames != nullptr, h_P != nullptr, h_dirs != nullptr, d_out != nullptr);
+    MMW_REQUIRE(n_resident >= 0 && V > 0 && S > 0 && C > 0, "bad shape: n_resident %d, V %d, S %d, C %d", n_resident, V, S, C);
+    MMW_REQUIRE(v >= 0 && v < V, "antenna v %d is not one of [0, %d)", v, V);
+    MMW_REQUIRE(k >= 1, "chirp stride k is %d", k);
+    MMW_REQUIRE(H >= 1, "window length H is %d", H);
+    MMW_REQUIRE(T >= 1, "T is %d steering directions", T);
+    MMW_REQUIRE(lambda_m > 0.0, "lambda_m %g is not positive", lambda_m);      // (a NaN fails too)
+    MMW_REQUIRE(n_out >= 0 && n_out <= 65535, "n_out %d is not in [0, 65535]", n_out);
+    MMW_REQUIRE((long)H * sa_cv(C, k) <= (1L << 24), "window of %d frames x %d chirps is longer than 2^24 elements", H, sa_cv(C, k));
+    for (int i = 0; i < n_out; ++i) {
+        MMW_REQUIRE(h_frames[i] >= 0 && h_frames[i] < n_resident, "h_frames[%d] = %d is not a resident frame of [0, %d)", i,
+                    h_frames[i], n_resident);
+        MMW_REQUIRE(i == 0 || h_frames[i] > h_frames[i - 1], "h_frames is not strictly ascending at %d (%d after %d)", i,
+                    h_frames[i], h_frames[i - 1]);
+    }
+    return MMW_OK;
 }
 
 }  // namespace mmw

@@ -9,29 +9,13 @@ extern template int launch_fft_axis<float, float>(mmw_ctx *, FftArgs, int, bool)
 
 using namespace mmw;
 
-// Every argument is judged here, before the context is touched: the function is not given the context, so a refused call cannot
-// enqueue anything and needs no device (tests/cpp/synth_array_sanitize.cpp relies on it).
-static int sa_validate(bool have_ctx, const void *d_cubes, int n_resident, int V, int S, int C, int v, int k, int H, const int *h_frames,
-                       int n_out, const double *h_P, const double *h_dirs, int T, double lambda_m, const void *d_out) {
-    MMW_REQUIRE(have_ctx && d_cubes && h_frames && h_P && h_dirs && d_out,
-                "null argument (ctx %d, d_cubes %d, h_frames %d, h_P %d, h_dirs %d, d_out %d)", (int)have_ctx, d_cubes != nullptr,
-                h_frames != nullptr, h_P != nullptr, h_dirs != nullptr, d_out != nullptr);
-    MMW_REQUIRE(n_resident >= 0 && V > 0 && S > 0 && C > 0, "bad shape: n_resident %d, V %d, S %d, C %d", n_resident, V, S, C);
-    MMW_REQUIRE(v >= 0 && v < V, "antenna v %d is not one of [0, %d)", v, V);
-    MMW_REQUIRE(k >= 1, "chirp stride k is %d", k);
-    MMW_REQUIRE(H >= 1, "window length H is %d", H);
-    MMW_REQUIRE(T >= 1, "T is %d steering directions", T);
-    MMW_REQUIRE(lambda_m > 0.0, "lambda_m %g is not positive", lambda_m);      // (a NaN fails too)
-    MMW_REQUIRE(n_out >= 0 && n_out <= 65535, "n_out %d is not in [0, 65535]", n_out);
-    MMW_REQUIRE((long)H * sa_cv(C, k) <= (1L << 24), "window of %d frames x %d chirps is longer than 2^24 elements", H, sa_cv(C, k));
-    for (int i = 0; i < n_out; ++i) {
-        MMW_REQUIRE(h_frames[i] >= 0 && h_frames[i] < n_resident, "h_frames[%d] = %d is not a resident frame of [0, %d)", i,
-                    h_frames[i], n_resident);
-        MMW_REQUIRE(i == 0 || h_frames[i] > h_frames[i - 1], "h_frames is not strictly ascending at %d (%d after %d)", i,
-                    h_frames[i], h_frames[i - 1]);
-    }
-    return MMW_OK;
+// The contraction for other units (mmw_tu_synth_calib.hip), so that the kernels are instantiated once, here.
+namespace mmw {
+int synth_array_contract(mmw_ctx *ctx, const char *family, const void *d_cubes, int V, int S, int C, int v, int k, int H, const int *d_frames,
+                         int n_out, const double *d_P, const double *d_dirs, int T, double lambda_m, void *d_out, size_t head) {
+    return synth_array_on(ctx, family, d_cubes, V, S, C, v, k, H, d_frames, n_out, d_P, d_dirs, T, lambda_m, d_out, head);
 }
+}  // namespace mmw
 
 extern "C" {
 

@@ -10,8 +10,10 @@ Host state here is two small scans (``gate`` and ``window_geometry``, both pure 
 ``batch.synthetic_array_geometry`` runs them for a whole sequence and ``FramePipeline.synthetic_array`` contracts every valid frame
 of a resident batch in one ``mmw_synth_array`` call, reading the windows in place.
 
-Left out on purpose: calibration against targets of opportunity (``enable_calibration=True`` raises ``NotImplementedError``) and
-the Cartesian ``griddata`` resampling of the image, which is presentation (and raises upstream for more than one elevation bin).
+Calibration against targets of opportunity is ``SelfCalibratingSyntheticArrayProcessor`` (below; batched as
+``FramePipeline.synthetic_array_calibrated`` on ``mmw_synth_array_calibrate``); the plain class keeps refusing
+``enable_calibration=True``.  Left out on purpose: the Cartesian ``griddata`` resampling of the image, which is presentation (and
+raises upstream for more than one elevation bin).
 """
 from __future__ import annotations
 
@@ -119,3 +121,101 @@ class SyntheticArrayBeamformerProcessor(_Processor):
             return np.empty(shape=0)
         self.beamformed_resp = self.compute_synthetic_response(self.array_geometry)
         return self.beamformed_resp
+
+
+# ---------------------------------------------------------------------------------------------------------------- self-calibration
+def calibration_spectra(window: np.ndarray) -> np.ndarray:
+    """``Fq [S, E]``: the range spectrum of every element of the window ``[S, E]`` under ``hamming(E)`` (no Hann over the samples)."""
+    window = np.asarray(window, dtype=complex)
+    return np.fft.fft(np.hamming(window.shape[1])[None, :] * window, axis=0)
+
+
+def calibration_targets(Fq: np.ndarray, response: np.ndarray):
+    """Up to three ``(range row, azimuth bin)`` pairs, strongest range row first: the three largest local maxima (value >= 0) of
+    the mean over elements of ``20 log10 |Fq|``, each with the first maximum among the local maxima of ``|10 log10 |response[row,
+    :, 0]||`` along azimuth; a row without a local maximum drops out.  Fewer than three range peaks, or a mean that is not finite
+    (a window slot of zeros), is "no suitable targets": ``[]`` (the reference indexes three peaks unconditionally and raises
+    ``IndexError`` there)."""
+    from scipy.signal import find_peaks
+    with np.errstate(divide="ignore"):
+        avg = np.mean(20 * np.log10(np.abs(Fq)), axis=1)
+    if not np.all(np.isfinite(avg)):
+        return []
+    peaks, _ = find_peaks(avg, height=0)
+    if len(peaks) < 3:
+        return []
+    rows = peaks[np.argsort(avg[peaks])[-3:][::-1]]
+    targets = []
+    for row in rows:
+        with np.errstate(divide="ignore"):
+            u = np.abs(10 * np.log10(np.abs(response[row, :, 0])))
+        az, _ = find_peaks(u, height=0)
+        if len(az):
+            targets.append((int(row), int(az[np.argmax(u[az])])))
+    return targets
+
+
+def calibrated_geometry(Fq: np.ndarray, P: np.ndarray, targets, d: np.ndarray, lambda_m: float) -> np.ndarray:
+    """``Pcal [3, E]``: per target the phase history of its range row steered to its direction, the unwrapped phase steps between
+    neighbouring elements, then per step the least-squares x / y displacement that explains the three steps
+    (``lstsq`` on ``(2 pi / lambda) d[0:2]`` of the targets, minimum norm when rank deficient) and its running sum taken off
+    ``P[0:2, 1:]``.  z is left alone."""
+    steer = np.array([d[:, a, 0] for _, a in targets])                                      # [3 targets, 3]
+    steps = np.stack([np.diff(np.unwrap(np.angle(Fq[r] * np.exp(2j * np.pi * (steer[t] @ P) / lambda_m))))
+                      for t, (r, _) in enumerate(targets)])                                 # [3, E - 1]
+    delta = np.linalg.lstsq(2 * np.pi / lambda_m * steer[:, 0:2], steps, rcond=None)[0]      # [2, E - 1]
+    out = np.array(P, dtype=float)
+    out[0:2, 1:] -= np.cumsum(delta, axis=1)
+    return out
+
+
+def calibrate_window(window: np.ndarray, P: np.ndarray, d: np.ndarray, lambda_m: float, num_iters: int, response: np.ndarray,
+                     contract):
+    """The calibration loop on one window ``[S, E]`` with geometry ``P [3, E]`` and uncalibrated image ``response [S, n_az, n_el]``;
+    ``contract(P)`` returns the image for a geometry.  Returns ``(response, Pcal, targets, status)``.  Two quirks of the reference
+    are kept: every iteration starts again from the UNCALIBRATED ``P`` (only the azimuth picks read the latest image, so
+    corrections do not accumulate), and an iteration that ends with fewer than three targets stops the loop, makes the calibrated
+    geometry the uncalibrated one and leaves the response of the iteration before."""
+    Fq = calibration_spectra(window)
+    Pcal, kept, status = np.array(P, dtype=float), [], 0
+    for _ in range(int(num_iters)):
+        targets = calibration_targets(Fq, response)
+        if len(targets) < 3:
+            Pcal = np.array(P, dtype=float)
+            break
+        Pcal = calibrated_geometry(Fq, P, targets, d, lambda_m)
+        response = contract(Pcal)
+        kept, status = targets, status + 1
+    return response, Pcal, kept, status
+
+
+class SelfCalibratingSyntheticArrayProcessor(SyntheticArrayBeamformerProcessor):
+    """``SyntheticArrayBeamformerProcessor`` with the reference's ``enable_calibration=True``: ``process`` returns the response of
+    the calibrated geometry.  After a valid frame ``array_geometry_calibrated [num_frames, 3, Cv]``, ``calibration_targets`` (the
+    picks of the last iteration that found three) and ``calibration_status`` (iterations that applied a correction) are set.  The
+    calibration runs in float64 numpy on the host history; the contractions go through ``SyntheticArrayBeamformerCore.contract``."""
+
+    def __init__(self, config_manager, *args, num_calibration_iters: int = 1, **kwargs):
+        if kwargs.pop("enable_calibration", True) is not True:
+            raise ValueError("SelfCalibratingSyntheticArrayProcessor calibrates: use SyntheticArrayBeamformerProcessor without")
+        if int(num_calibration_iters) < 1:
+            raise ValueError(f"num_calibration_iters is {num_calibration_iters}")
+        self.num_calibration_iters = int(num_calibration_iters)
+        self.array_geometry_calibrated = np.empty(shape=0)
+        self.calibration_targets, self.calibration_status = [], 0
+        super().__init__(config_manager, *args, enable_calibration=False, **kwargs)
+
+    def process(self, adc_cube: np.ndarray, current_vel, **kwargs) -> np.ndarray:
+        resp = super().process(adc_cube, current_vel, **kwargs)
+        if not self.array_geometry_valid:
+            return resp
+        hist = self.history_acd_cube_valid_chirps
+        window = hist.transpose(1, 0, 2).reshape(hist.shape[1], -1)
+        H = self.num_frames
+        P = self.array_geometry.transpose(1, 0, 2).reshape(3, -1)
+        contract = lambda g: self.compute_synthetic_response(g.reshape(3, H, -1).transpose(1, 0, 2))       # noqa: E731
+        resp, Pcal, self.calibration_targets, self.calibration_status = calibrate_window(
+            window, P, self.d, self.lambda_m, self.num_calibration_iters, resp, contract)
+        self.array_geometry_calibrated = Pcal.reshape(3, H, -1).transpose(1, 0, 2)
+        self.beamformed_resp = resp
+        return resp
