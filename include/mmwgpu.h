@@ -310,6 +310,63 @@ int mmw_doppler_azimuth_peaks(mmw_ctx *ctx, const float *d_maps, int n_sets, int
 int mmw_diag_doppler_azimuth_peaks_host(const float *h_maps, int n_sets, int F, int n_rows, int A, const int32_t *h_groups, int G,
                                         const int32_t *h_m, int a_lo, int a_hi, int a_zero, double min_threshold_dB,
                                         double prominence_dB, int32_t *h_row_peak, int32_t *h_zero);
+/* mmw_doppler_azimuth_ransac: the regression stage of the Doppler-azimuth velocity estimator (processors/velocity_estimator.py:
+ *   estimate_ego_vx_velocity :640-661, lsq_fit_ego_vy_ransac :346-506) on the index tables mmw_doppler_azimuth_peaks leaves in
+ *   HBM, one fit per (group, frame), nothing downloaded:
+ *     d_row_peak int32 [G][F][n_rows], d_zero int32 [G][F] (-1: none, -2: undecided);  h_m host int32 [F]: the rows of each
+ *     frame (NULL: n_rows), rows >= m[f] are absent;  d_vel float64: one table [vel_len] for all frames (vel_per_frame == 0) or
+ *     [F][vel_len] (the precise mode's zoomed_vel_bins), vel_len >= n_rows;  d_cos, d_sin, d_theta float64 [n_cols]: np.cos,
+ *     np.sin of the valid angle bins and the bins themselves;  d_subsets int32 [n_tab][20][10]: row N - 10 holds the subsets
+ *     scikit-learn draws for N points (ransac_tables.subset_table(N)), n_tab >= n_rows - 9;  d_trials int32 [trials_len]: the
+ *     trial caps of N points (ransac_tables.trials_table(N), N + 1 entries) one behind the other from N = 10 to 9 + n_tab.
+ *     vx = -1 * (v_az + v_el) / 2.0, -1 * v or 0.0 from the zero-azimuth entries of groups g_az and g_el (g_el == -1: no elevation
+ *     group), in NumPy's operation order: bit-equal.  The peak list of (g, f) are its rows with an entry >= 0, in row order, N of
+ *     them.  vx >= MMW_DOPAZ_VX_BRANCH: y = (-1 * v) - (vx * cos), H = sin, threshold thr_standard, vy = coef, R^2 of the refit on
+ *     its inliers (0.0 with at most 3);  else y = theta, H = v - vx, threshold thr_small_vx, vy = -1 / a (0 for a == 0), R^2
+ *     without the inlier gate.  The fit is RANSACRegressor(LinearRegression(fit_intercept=False), min_samples=10, max_trials=20,
+ *     random_state=42) of scikit-learn 1.7.2, walked in its order.
+ *     d_out float64 [G][F][4] = (vx, vy, R^2, inlier share);  d_flags int32 [G][F]: MMW_DOPAZ_FLAG_* bits in the low byte, the
+ *     status MMW_DOPAZ_STATUS_* at MMW_DOPAZ_STATUS_SHIFT, the inlier count at MMW_DOPAZ_INLIERS_SHIFT.  STATUS_EMPTY: N == 0 (the
+ *     caller keeps the previous frame's values);  STATUS_FAILED: N < 10 or no accepted trial (the class's ValueError path), row
+ *     (vx, 0, 0, 0).  A decision rounding could turn against scikit-learn's SVD solve sets a flag bit and zeroes the row: the
+ *     caller refits that pair on the host.  mode MMW_DOPAZ_RANSAC_VX_ONLY: only vx (x_measurement_only).
+ *   One wavefront per (group, frame), four to a workgroup; profile family "dopaz_ransac".
+ *   MMW_ERR_INVALID (nothing launched, outputs untouched; the text names what was refused): a null pointer (h_m excepted), a
+ *   negative count, g_az outside [0, G) or g_el outside [-1, G), m[f] outside [0, n_rows], vel_len < n_rows, n_cols < 1, tables
+ *   that do not serve n_rows (n_tab, trials_len), a threshold that is not finite, element counts beyond 2^31 - 1.
+ *   MMW_ERR_UNSUPPORTED: n_rows > MMW_DOPAZ_RANSAC_MAX_ROWS.  F == 0 or G == 0: MMW_OK, nothing launched.
+ * mmw_diag_doppler_azimuth_ransac_host: the same rule (one implementation, mmw_dopaz_velocity.h, the 64 lanes as a loop) on host
+ *   pointers; no context, no device.  Rows and flags are bit-identical to the kernel's. */
+#define MMW_DOPAZ_VX_BRANCH 0.1
+#define MMW_DOPAZ_RANSAC_MAX_ROWS 512
+#define MMW_DOPAZ_RANSAC_VX_ONLY 1
+#define MMW_DOPAZ_FLAG_RESIDUAL 1    /* a residual within the band of the threshold in a trial */
+#define MMW_DOPAZ_FLAG_SCORE_TIE 2   /* equal inlier counts, scores within the band, different inlier sets */
+#define MMW_DOPAZ_FLAG_R2 4          /* R^2 within the band of min_R2, or ill-defined */
+#define MMW_DOPAZ_FLAG_SHARE 8       /* the inlier share at min_inlier_share */
+#define MMW_DOPAZ_FLAG_A_ZERO 16     /* the small-vx coefficient within the band of 0 */
+#define MMW_DOPAZ_FLAG_NONFINITE 32  /* a non-finite table entry, or sums beyond the trusted range */
+#define MMW_DOPAZ_FLAG_UNDECIDED 64  /* a -2 among the pair's inputs */
+#define MMW_DOPAZ_FLAG_TABLES 128    /* an entry that is no index of its table (caller error; nothing computed) */
+#define MMW_DOPAZ_FLAG_MASK 0xff
+#define MMW_DOPAZ_STATUS_SHIFT 8
+#define MMW_DOPAZ_STATUS_OK 0
+#define MMW_DOPAZ_STATUS_EMPTY 1
+#define MMW_DOPAZ_STATUS_FAILED 2
+#define MMW_DOPAZ_STATUS_MASK 3
+#define MMW_DOPAZ_INLIERS_SHIFT 16
+int mmw_doppler_azimuth_ransac(mmw_ctx *ctx, const int32_t *d_row_peak, const int32_t *d_zero, int G, int F, int n_rows,
+                               const int32_t *h_m, const double *d_vel, int vel_len, int vel_per_frame, const double *d_cos,
+                               const double *d_sin, const double *d_theta, int n_cols, const int32_t *d_subsets,
+                               const int32_t *d_trials, int n_tab, int trials_len, int g_az, int g_el, int mode,
+                               double thr_standard, double thr_small_vx, double min_R2, double min_inlier_share, double *d_out,
+                               int32_t *d_flags);
+int mmw_diag_doppler_azimuth_ransac_host(const int32_t *h_row_peak, const int32_t *h_zero, int G, int F, int n_rows,
+                                         const int32_t *h_m, const double *h_vel, int vel_len, int vel_per_frame,
+                                         const double *h_cos, const double *h_sin, const double *h_theta, int n_cols,
+                                         const int32_t *h_subsets, const int32_t *h_trials, int n_tab, int trials_len, int g_az,
+                                         int g_el, int mode, double thr_standard, double thr_small_vx, double min_R2,
+                                         double min_inlier_share, double *h_out, int32_t *h_flags);
 
 /* mmw_range_profile: d_out[F][S] float32 = mean_rx | FFT_S( hann(S) x[:, :, chirp] ) |
  *   replaces RangeProcessor.coarse_fft (processors/range_resp.py:32-57).

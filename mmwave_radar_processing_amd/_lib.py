@@ -29,6 +29,12 @@ QUEUE_COMPUTE, QUEUE_COPY = 0, 1
 CELLS64_DENSE, CELLS64_DIRECT, CELLS64_DENSE_MIXED = 0, 1, 2
 DOPAZ_PEAK_BAND = 1e-10  # include/mmwgpu.h MMW_DOPAZ_PEAK_BAND: the relative band inside which the peak pickers do not decide
 DOPAZ_PEAK_NONE, DOPAZ_PEAK_UNDECIDED = -1, -2
+# include/mmwgpu.h MMW_DOPAZ_*: the flag word of mmw_doppler_azimuth_ransac
+DOPAZ_VX_BRANCH, DOPAZ_RANSAC_MAX_ROWS, DOPAZ_RANSAC_VX_ONLY = 0.1, 512, 1
+DOPAZ_FLAG_RESIDUAL, DOPAZ_FLAG_SCORE_TIE, DOPAZ_FLAG_R2, DOPAZ_FLAG_SHARE = 1, 2, 4, 8
+DOPAZ_FLAG_A_ZERO, DOPAZ_FLAG_NONFINITE, DOPAZ_FLAG_UNDECIDED, DOPAZ_FLAG_TABLES = 16, 32, 64, 128
+DOPAZ_FLAG_MASK, DOPAZ_STATUS_SHIFT, DOPAZ_STATUS_MASK, DOPAZ_INLIERS_SHIFT = 0xff, 8, 3, 16
+DOPAZ_STATUS_OK, DOPAZ_STATUS_EMPTY, DOPAZ_STATUS_FAILED = 0, 1, 2
 
 
 class MmwGpuError(RuntimeError):
@@ -90,6 +96,10 @@ _SIGNATURES = {
     "mmw_doppler_azimuth_zoom_batch": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _i, _ip, _ip, _i, _i, C.POINTER(_d), _i],
     "mmw_doppler_azimuth_peaks": [_vp, _vp, _i, _i, _i, _i, _ip, _i, _ip, _i, _i, _i, _d, _d, _vp, _vp],
     "mmw_diag_doppler_azimuth_peaks_host": [_vp, _i, _i, _i, _i, _ip, _i, _ip, _i, _i, _i, _d, _d, _vp, _vp],
+    "mmw_doppler_azimuth_ransac": [_vp, _vp, _vp, _i, _i, _i, _ip, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i,
+                                   _d, _d, _d, _d, _vp, _vp],
+    "mmw_diag_doppler_azimuth_ransac_host": [_vp, _vp, _i, _i, _i, _ip, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i,
+                                             _d, _d, _d, _d, _vp, _vp],
     "mmw_range_profile": [_vp, _vp, _vp, _i, _i, _i, _i, _i],
     "mmw_range_profile_f64": [_vp, _vp, _vp, _i, _i, _i, _i, _i],
     "mmw_range_zoom": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d],

@@ -834,6 +834,140 @@ class FramePipeline:
         self.n_peaks_undecided = int(undecided.sum())
         return row_peaks, zero_az
 
+    def doppler_azimuth_fits(self, estimator, altitudes, enable_precise_responses=False):
+        """Stages 1 to 3 of ``processors.velocity_estimator.VelocityEstimator.process`` (the ADC-cube path) for every resident
+        frame: ``(fits [F, G, 4], status [F, G])`` with ``fits[f, g] = (vx, vy, R^2, inlier share)`` of group g (0: azimuth,
+        1: elevation on an ods array) and ``status`` one of ``_lib.DOPAZ_STATUS_OK / _EMPTY / _FAILED`` -- what ``dopaz_state_scan``
+        turns into the estimator's track.  Range windows, antenna sets, valid angle columns, the peak threshold and the gates are
+        read from the estimator as ``process`` derives them; ``altitudes``: one per frame, or one for all.
+
+        The maps, the peak picker and ``mmw_doppler_azimuth_ransac`` run on the device, the regression on the index tables the
+        picker left in HBM.  With ``enable_precise_responses`` the coarse pass gives vx, ``precise_ranges_from_zero_az`` the
+        velocity ranges, and the precise maps, picker and fit follow (the reference's order).  A pair the kernel flagged is
+        refitted by the estimator's own scikit-learn function from that pair's peaks (picked again by the host pickers from the
+        frame's downloaded maps where its tables held a -2); ``self.n_dopaz_fits_flagged`` counts them.  ``x_measurement_only``
+        estimators run the zero-azimuth part only.  The estimator is only read."""
+        import copy
+        from .point_cloud_processing import ransac_tables
+        from .processors import velocity_estimator as ve
+        # every argument check comes before the first use of self.ctx / self.bufs
+        if not isinstance(estimator, ve.VelocityEstimator):
+            raise ValueError("doppler_azimuth_fits: estimator must be a processors.velocity_estimator.VelocityEstimator, got "
+                             f"{type(estimator).__name__}")
+        F = self.n_frames
+        alt = np.asarray(altitudes, dtype=np.float64)
+        if alt.ndim == 0:
+            alt = np.full(F, float(alt))
+        if alt.shape != (F,) or not np.all(np.isfinite(alt)):
+            raise ValueError(f"doppler_azimuth_fits: altitudes must be {F} finite numbers (one per resident frame) or one, got "
+                             f"shape {alt.shape}")
+        gates = (float(estimator.min_R2_threshold), float(estimator.min_inlier_percent))
+        if not np.all(np.isfinite(gates)):
+            raise ValueError(f"doppler_azimuth_fits: the estimator's gates must be finite, got {gates}")
+        cm = estimator.config_manager
+        sets, groups, shift = ve.antenna_plan(cm)
+        G = len(groups)
+        windows = np.stack([estimator.get_range_window(altitude=a, sensing_direction=cm.array_direction) for a in alt]) \
+            if F else np.zeros((0, 2))
+        thr_dB = estimator.peak_threshold_dB
+        theta = np.ascontiguousarray(estimator.valid_angle_bins, dtype=np.float64)
+        mode = _lib.DOPAZ_RANSAC_VX_ONLY if estimator.x_measurement_only else 0
+        pv = None
+        if enable_precise_responses:
+            _, zero_az = self.doppler_azimuth_peaks(estimator, sets, groups, windows, shift, None, thr_dB)
+            pv = precise_ranges_from_zero_az(zero_az[0], zero_az[1] if G == 2 else None, estimator.precise_vel_bound)
+        row_peak, zero, m, bins = self.doppler_azimuth_peaks_device(estimator, sets, groups, windows, shift, pv, thr_dB)
+        d, shape = self.dopaz_peak_maps
+        n_rows = row_peak.shape[2]
+        fits = np.zeros((F, G, 4))
+        status = np.full((F, G), _lib.DOPAZ_STATUS_EMPTY, dtype=np.int32)
+        self.n_dopaz_fits_flagged = 0
+        if F == 0:
+            return fits, status
+        if m is None:
+            rows_of = np.full(F, n_rows, dtype=np.int64)
+            vel = np.ascontiguousarray(estimator.vel_bins, dtype=np.float64)
+            vel_of = lambda f: vel                      # noqa: E731
+        else:
+            rows_of = np.asarray(m, dtype=np.int64)
+            vel = np.zeros((F, max(n_rows, 1)))
+            for f in range(F):
+                vel[f, :rows_of[f]] = bins[f]
+            vel_of = lambda f: vel[f]                   # noqa: E731
+        flags = np.zeros((G, F), dtype=np.int32)
+        if d is not None and n_rows > 0:
+            subsets, trials = ransac_tables.dopaz_tables(n_rows)
+            key = ("dopaz_ransac_tables", n_rows)
+            if getattr(self, "_dopaz_ransac_key", None) != key:          # uploaded once per n_rows and kept
+                self.bufs.get("dopaz_ransac_subsets", subsets.nbytes).upload(subsets)
+                self.bufs.get("dopaz_ransac_trials", trials.nbytes).upload(trials)
+                self._dopaz_ransac_key = key
+            d_sub = self.bufs.get("dopaz_ransac_subsets", subsets.nbytes)
+            d_tri = self.bufs.get("dopaz_ransac_trials", trials.nbytes)
+            angles = np.ascontiguousarray(np.stack([np.cos(theta), np.sin(theta), theta]))
+            d_ang = self.bufs.get("dopaz_ransac_angles", angles.nbytes)
+            if getattr(self, "_dopaz_ransac_angles", None) != angles.tobytes():   # they change with the estimator only
+                d_ang.upload(angles)
+                self._dopaz_ransac_angles = angles.tobytes()
+            d_vel = self.bufs.get("dopaz_ransac_vel", vel.nbytes)
+            d_vel.upload(vel)
+            d_row = self.bufs.get("dopaz_row_peak", row_peak.nbytes)
+            d_zero = self.bufs.get("dopaz_zero_peak", zero.nbytes)
+            d_out = self.bufs.get("dopaz_ransac_out", G * F * 32)
+            d_flags = self.bufs.get("dopaz_ransac_flags", G * F * 4)
+            h_m = None if m is None else np.ascontiguousarray(m, dtype=np.int32)
+            nc = len(theta)
+            _lib.check(self.ctx.lib.mmw_doppler_azimuth_ransac(
+                self.ctx.handle, d_row.ptr, d_zero.ptr, G, F, n_rows, None if h_m is None else h_m.ctypes.data_as(_lib._ip),
+                d_vel.ptr, vel.shape[-1], int(vel.ndim == 2), d_ang.ptr, d_ang.at(nc * 8), d_ang.at(2 * nc * 8), nc, d_sub.ptr,
+                d_tri.ptr, max(n_rows - ransac_tables.MIN_SAMPLES + 1, 0), len(trials), 0, 1 if G == 2 else -1, mode,
+                ve.THRESHOLD_STANDARD, ve.THRESHOLD_SMALL_VX, gates[0], gates[1], d_out.ptr, d_flags.ptr))
+            fits = d_out.download((G, F, 4), np.float64).transpose(1, 0, 2).copy()
+            flags = d_flags.download((G, F), np.int32).copy()
+            status = ((flags >> _lib.DOPAZ_STATUS_SHIFT) & _lib.DOPAZ_STATUS_MASK).T.astype(np.int32)
+        # pairs the device left to the host: the frame's peaks (picked again where a table entry is undecided), the class's fit
+        redo = (flags & _lib.DOPAZ_FLAG_MASK) != 0           # no maps (a batch without velocity rows): every pair is empty
+        self.n_dopaz_fits_flagged = int(redo.sum())
+        if redo.any():
+            table = _peak_groups(groups, shape[0], np.zeros(shape[0], dtype=bool))
+            mask = np.asarray(estimator.valid_angle_mask, dtype=bool)
+            tmp = copy.copy(estimator)
+            for f in np.flatnonzero(redo.any(axis=0)):
+                mf, v = int(rows_of[f]), vel_of(f)
+                picked = []
+                for g in range(G):
+                    if d is not None and (np.any(row_peak[g, f, :mf] == _lib.DOPAZ_PEAK_UNDECIDED) or zero[g, f] == _lib.DOPAZ_PEAK_UNDECIDED):
+                        frame_bytes = n_rows * shape[3] * 4
+                        maps = [d.download((n_rows, shape[3]), np.float32, (int(k) * F + f) * frame_bytes).astype(np.float64)
+                                for k in table[g] if k >= 0]
+                        resp = (maps[0] if len(maps) == 1 else (maps[0] + maps[1]) / 2)[:mf, mask]
+                        picked.append((estimator.detect_peaks_rows(resp, v[:mf], thr_dB), estimator.detect_peak_zero_az(resp, v[:mf], thr_dB)))
+                    else:
+                        rows = np.flatnonzero(row_peak[g, f, :mf] >= 0)
+                        z = int(zero[g, f])
+                        picked.append((np.stack([theta[row_peak[g, f, rows]], v[rows]], axis=1),
+                                       np.array([0.0, v[z]]) if z >= 0 else np.empty(shape=(0, 2))))
+                tmp.azimuth_peak_zero_az = picked[0][1]
+                tmp.elevation_peak_zero_az = picked[1][1] if G == 2 else np.empty(shape=(0, 2))
+                vx = tmp.estimate_ego_vx_velocity()
+                for g in np.flatnonzero(redo[:, f]):
+                    peaks = picked[g][0]
+                    if mode or peaks.shape[0] == 0:
+                        fits[f, g] = (vx, 0.0, 0.0, 0.0)
+                        status[f, g] = _lib.DOPAZ_STATUS_OK if mode else _lib.DOPAZ_STATUS_EMPTY
+                        continue
+                    fit = tmp.lsq_fit_ego_vy_ransac(peaks=peaks)
+                    fits[f, g] = (vx,) + tuple(fit)
+                    status[f, g] = _lib.DOPAZ_STATUS_FAILED if tuple(fit) == (0.0, 0.0, 0.0) else _lib.DOPAZ_STATUS_OK
+        return fits, status
+
+    def doppler_azimuth_velocities(self, estimator, altitudes, enable_precise_responses=False) -> np.ndarray:
+        """``estimator.process(adc_cube=cube_f, altitude=altitudes[f], enable_precise_responses=...)`` of every resident frame in
+        order: ``[F, 3]`` current estimates.  ``doppler_azimuth_fits`` and then ``dopaz_state_scan``, which advances the estimator
+        (its state carries across calls and ``stream()`` chunks)."""
+        fits, status = self.doppler_azimuth_fits(estimator, altitudes, enable_precise_responses)
+        return dopaz_state_scan(estimator, fits, status)
+
     def synthetic_array_device(self, proc, velocities) -> Tuple[np.ndarray, _lib.DeviceBuffer]:
         """``(frames, buffer)``: the images of ``synthetic_array`` left in HBM, complex64 ``[n_valid][S][n_az * n_el]``, nothing
         downloaded."""
@@ -1368,6 +1502,34 @@ def ego_state_scan(estimator, fits: np.ndarray, counts: Sequence[int]) -> np.nda
     return out
 
 
+def dopaz_state_scan(estimator, fits: np.ndarray, status: np.ndarray) -> np.ndarray:
+    """Advance a ``processors.velocity_estimator.VelocityEstimator`` over the frames of ``FramePipeline.doppler_azimuth_fits``:
+    ``fits [F, G, 4]`` (vx, vy, R^2, share), ``status [F, G]``; returns the ``[F, 3]`` current estimates, as stepping
+    ``process(adc_cube=...)`` frame by frame would.  An empty group keeps the fit its direction had (the class fits only
+    directions with row peaks), a failed fit installs zeros, the proposal is formed in the geometry's component order and the
+    gates are the class's own.  The estimator's state carries over to the next call."""
+    fits = np.asarray(fits, dtype=np.float64)
+    status = np.asarray(status)
+    if fits.ndim != 3 or fits.shape[2] != 4 or status.shape != fits.shape[:2]:
+        raise ValueError(f"dopaz_state_scan: fits must be [F, G, 4] and status [F, G], got {fits.shape} and {status.shape}")
+    geometry = estimator.config_manager.array_geometry
+    G = {"standard": 1, "ods": 2}.get(geometry)
+    if G is None or fits.shape[1] != G:
+        raise ValueError(f"dopaz_state_scan: a {geometry} array has {G} groups, the fits hold {fits.shape[1]}")
+    out = np.zeros((len(fits), 3))
+    for f in range(len(fits)):
+        estimator.ego_vx_estimate = float(fits[f, 0, 0])
+        took = [None if status[f, g] == _lib.DOPAZ_STATUS_EMPTY else
+                ((0.0, 0.0, 0.0) if status[f, g] == _lib.DOPAZ_STATUS_FAILED else tuple(float(x) for x in fits[f, g, 1:]))
+                for g in range(G)]
+        if estimator.x_measurement_only:
+            took = []
+        estimator.take_fits(*took)
+        estimator.update_and_check_current_vel_measurements()
+        out[f] = estimator.current_velocity_estimate
+    return out
+
+
 class MultiDeviceFramePipeline:
     """One process, every visible device: the frame range is block-split (``shard_bounds``) over one ``FramePipeline``
     per device, each driven by its own host thread (a context is only ever touched by its thread), results land in
@@ -1490,6 +1652,26 @@ class MultiDeviceFramePipeline:
             raise RuntimeError(f"joined {len(counts)} per-frame fits for {self.n_frames} frames")
         self.n_ego_flagged = sum(getattr(self.parts[r], "n_ego_flagged", 0) for r in live)
         return ego_state_scan(estimator, fits, counts)
+
+    def doppler_azimuth_velocities(self, estimator, altitudes, enable_precise_responses=False) -> np.ndarray:
+        """``FramePipeline.doppler_azimuth_velocities``: every device fits the frames of its shard (``doppler_azimuth_fits`` with
+        its rows of ``altitudes``), the estimator's state runs once over the joined fits in frame order."""
+        alt = np.asarray(altitudes, dtype=np.float64)
+        if alt.ndim == 0:
+            alt = np.full(self.n_frames, float(alt))
+        if alt.shape != (self.n_frames,):
+            raise ValueError(f"doppler_azimuth_velocities: altitudes must be {self.n_frames} numbers or one, got shape {alt.shape}")
+        live = [r for r in range(self.world) if self.bounds[r][1] > self.bounds[r][0]]
+        per_rank = self._each(lambda r: self.parts[r].doppler_azimuth_fits(estimator, alt[self.bounds[r][0]:self.bounds[r][1]],
+                                                                          enable_precise_responses))
+        if not per_rank:
+            return np.zeros((0, 3))
+        fits = np.concatenate([f for f, _ in per_rank])
+        status = np.concatenate([s for _, s in per_rank])
+        if len(fits) != self.n_frames:
+            raise RuntimeError(f"joined {len(fits)} per-frame fits for {self.n_frames} frames")
+        self.n_dopaz_fits_flagged = sum(getattr(self.parts[r], "n_dopaz_fits_flagged", 0) for r in live)
+        return dopaz_state_scan(estimator, fits, status)
 
     def micro_doppler(self, target_ranges=(0, 1.0), rx_idx: int = 0) -> np.ndarray:
         """``FramePipeline.micro_doppler`` of every shard, concatenated in frame order (the rows are independent of each other;

@@ -101,3 +101,28 @@ def frame_tables(counts: Sequence[int]) -> Tuple[np.ndarray, np.ndarray, np.ndar
         row[counts == n] = r
     tab = np.concatenate(tabs) if tabs else np.zeros(1, dtype=np.int32)
     return subsets[:len(sizes)] if len(sizes) else subsets[:0], row, tab, offs[:len(sizes)]
+
+
+_dopaz: Dict[int, Tuple[np.ndarray, np.ndarray]] = {}
+
+
+def dopaz_tables(n_rows: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The two table arguments of ``mmw_doppler_azimuth_ransac`` for peak lists of up to ``n_rows`` pairs, made once per
+    ``n_rows`` and kept: ``subsets`` int32 ``[n_tab, 20, 10]`` with row N - 10 the draws for N pairs, and ``trials``, the
+    ``trials_table_full(N)`` rows (N + 1 entries each) one behind the other, for N = 10 .. n_rows.  The kernel indexes both by
+    the N it counted.  Below 10 rows no fit is possible: ``n_tab`` is 0 and both arrays hold one unused entry."""
+    n_rows = int(n_rows)
+    tabs = _dopaz.get(n_rows)
+    if tabs is None:
+        sizes = range(MIN_SAMPLES, n_rows + 1)
+        subsets = np.zeros((max(len(sizes), 1), MAX_TRIALS, MIN_SAMPLES), dtype=np.int32)
+        trials = [np.zeros(1, dtype=np.int32)] if not len(sizes) else []
+        for row, n in enumerate(sizes):
+            subsets[row] = subset_table(n)
+            t = trials_table(n)
+            trials.append(t)
+        tabs = (subsets, np.ascontiguousarray(np.concatenate(trials), dtype=np.int32))
+        for t in tabs:
+            t.setflags(write=False)
+        _dopaz[n_rows] = tabs
+    return tabs

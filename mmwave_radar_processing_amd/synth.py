@@ -103,3 +103,54 @@ def synth_ground_sequence(seed: int, n_frames: int = 5, shape=(12, 256, 128), ra
         x += noise_sigma * (rng.standard_normal(shape) + 1j * rng.standard_normal(shape))
         cubes[f] = (np.rint(x.real) + 1j * np.rint(x.imag)).astype(np.complex64)
     return cubes
+
+
+# element positions (azimuth, elevation) in half wavelengths of the 12 virtual antennas, consistent with the antenna sets of
+# processors/velocity_estimator.py: along an azimuth set the first coordinate counts up, along an elevation set the second
+PLATFORM_LAYOUT = {
+    "standard": [(k, 0) for k in range(8)] + [(k, 1) for k in range(2, 6)],
+    "ods": [(0, 3), (0, 2), (1, 2), (1, 3), (2, 3), (2, 2), (3, 2), (3, 3), (2, 1), (2, 0), (3, 0), (3, 1)],
+}
+
+
+def synth_moving_platform_sequence(seed: int, n_frames: int, shape=(12, 256, 128), range_res_m: float = 0.0975887,
+                                   vel_res_m_s: float = 0.05, geometry: str = "standard", range_window_m=(0.6, 2.4),
+                                   velocities=None, num_scatterers: int = 48, noise_sigma: float = 20.0, movers=None,
+                                   dropouts=()):
+    """``(cubes [n_frames, V, S, C], velocities [n_frames, 2])``: a static scene seen from a moving platform.  Every frame has
+    ``num_scatterers`` point scatterers of its own, spread over azimuth and elevation (+-60 degrees) at ranges inside
+    ``range_window_m``; a scatterer at azimuth theta shows the Doppler velocity -(vx cos(theta) + vy sin(theta)) for the frame's
+    ``(vx, vy)``, which drifts from frame to frame (``velocities=None``: vx from 0.3 up by 0.04 per frame, vy from -0.5 up by
+    0.03) -- the cosine law the Doppler-azimuth velocity estimator regresses.  ``movers[f]`` of frame f's scatterers (behind the
+    boresight one) move on their own: a Doppler velocity drawn from +-20 velocity bins instead of the law's.  Frames listed in
+    ``dropouts`` are all zeros (a lost frame: no peak anywhere).  Antenna phases follow ``PLATFORM_LAYOUT``.
+    Deterministic from ``seed``; integer-valued complex64 like ``synth_cube``."""
+    V, S, C = shape
+    layout = np.array(PLATFORM_LAYOUT[geometry][:V], dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    if velocities is None:
+        velocities = np.stack([0.3 + 0.04 * np.arange(n_frames), -0.5 + 0.03 * np.arange(n_frames)], axis=1)
+    velocities = np.asarray(velocities, dtype=np.float64).reshape(n_frames, 2)
+    n = np.arange(S)[None, :, None]
+    m = np.arange(C)[None, None, :]
+    cubes = np.empty((n_frames,) + tuple(shape), dtype=np.complex64)
+    for f in range(n_frames):
+        x = np.zeros(shape, dtype=np.complex128)
+        theta = rng.uniform(-np.pi / 3, np.pi / 3, num_scatterers)
+        phi = rng.uniform(-np.pi / 3, np.pi / 3, num_scatterers)
+        theta[0] = phi[0] = 0.0                                       # one scatterer on boresight: the zero-azimuth peak
+        rng_m = rng.uniform(range_window_m[0], range_window_m[1], num_scatterers)
+        amp = rng.uniform(150.0, 400.0, num_scatterers)
+        vd = -(velocities[f, 0] * np.cos(theta) + velocities[f, 1] * np.sin(theta))
+        n_movers = 0 if movers is None else int(movers[f])
+        vd[1:1 + n_movers] = rng.uniform(-20.0, 20.0, n_movers) * vel_res_m_s
+        if f in dropouts:
+            cubes[f] = 0
+            continue
+        for k in range(num_scatterers):
+            ant = np.pi * (layout[:, 0] * np.sin(theta[k]) + layout[:, 1] * np.sin(phi[k]))[:, None, None]
+            x += amp[k] * np.exp(1j * (2.0 * np.pi * (rng_m[k] / range_res_m / S * n + vd[k] / vel_res_m_s / C * m) + ant
+                                       + rng.uniform(0, 2 * np.pi)))
+        x += noise_sigma * (rng.standard_normal(shape) + 1j * rng.standard_normal(shape))
+        cubes[f] = (np.rint(x.real) + 1j * np.rint(x.imag)).astype(np.complex64)
+    return cubes, velocities
