@@ -184,11 +184,41 @@ int mmw_dbs_sharpen(mmw_ctx *ctx, const void *d_cubes, void *d_rd, const int32_t
  *   MicroDopplerProcessor.process (processors/micro_doppler_resp.py:91-114) rolls into its spectrogram: |fftshift(fft2(x[rx]))|,
  *   the rows of the range window, np.max over them.  Only antenna rx_idx's [S][C] slab of a frame is read, only the rows of the
  *   window are computed (a partial DFT over fast time, direct DFTs over slow time, float32), and nothing but the C floats of a
- *   frame is written.  Any S, C >= 1 up to 3400 chirps (MMW_ERR_UNSUPPORTED beyond: the rows in flight live in the LDS).
+ *   frame is written.  Any S, C >= 1 up to 3444 chirps (MMW_ERR_UNSUPPORTED beyond: the rows in flight live in the LDS).
  *   MMW_ERR_INVALID (nothing launched, d_out untouched): a null pointer, n_frames < 0, rx_idx outside [0, V), row_lo > row_hi,
  *   a row outside [0, S).  n_frames == 0: MMW_OK, nothing launched.  Profile family "micro_doppler". */
 int mmw_micro_doppler(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C, int rx_idx, int row_lo,
                       int row_hi);
+/* mmw_sar_slices: per frame f one window of the un-windowed range-Doppler plane of antenna rx_idx, complex64, packed:
+ *     block f = d_out + h_off[f], row-major [row_hi - row_lo][col_hi - col_lo],
+ *     block_f[r - row_lo][c - col_lo] = sum_s sum_j x_f[rx_idx][s][j] exp(-2 pi i (r s / S + j k / C)),   k = (c + C - C/2) mod C,
+ *   i.e. np.fft.fftshift(np.fft.fft2(x), axes=1)[row_lo:row_hi, col_lo:col_hi] (odd C included): what StripMapSARProcessor.process
+ *   (processors/strip_map_SAR_processor.py:160-194) keeps of the plane -- [valid_ranges_slice, valid_angles_slice], the columns
+ *   a function of that frame's platform speed (:108-158), hence a window per frame and a ragged output.  h_win[F][4] holds
+ *   (row_lo, row_hi, col_lo, col_hi), half open; h_off[F + 1] the blocks' first elements in complex64 units, h_off[F] the total.
+ *   Both are host arrays, free again when the call returns.  Only antenna rx_idx's [S][C] slab of a frame is read, only the listed
+ *   rows and columns are computed (a partial DFT over fast time, direct DFTs over slow time, float32), and nothing but the blocks
+ *   is written; a frame whose window is empty in either axis writes nothing.  Any S >= 1 and any C <= 3444 -- the shapes
+ *   mmw_micro_doppler serves (MMW_ERR_UNSUPPORTED beyond: the rows in flight live in the LDS; the shape is judged before the
+ *   windows, so also when every window is empty, where a served shape returns MMW_OK with nothing launched).  The grid is capped at 4096
+ *   workgroups; with more frames a workgroup walks frames f, f + 4096, ...
+ *   MMW_ERR_INVALID (nothing launched, d_out untouched): a null pointer, n_frames < 0, rx_idx outside [0, V), a window reversed
+ *   or outside [0, S] x [0, C], h_off[0] != 0, h_off[f + 1] - h_off[f] different from the window's area.  n_frames == 0: MMW_OK,
+ *   nothing launched.  Profile family "sar_slices". */
+int mmw_sar_slices(mmw_ctx *ctx, const void *d_cubes, int n_frames, int V, int S, int C, int rx_idx,
+                   const int32_t *h_win /* [F][4]: row_lo,row_hi,col_lo,col_hi, half open */,
+                   const int64_t *h_off /* [F+1], in complex64 elements */, void *d_out);
+/* mmw_range_detect: RangeDetector.process (processors/range_detector.py:59-83) for F frames in one call, no host round trip:
+ *   the float64 range profile of chirp chirp_idx (mmw_range_profile_f64's values; into d_profile[F][S], or library scratch when
+ *   NULL), the 1-D CFAR of mmw_cfar1d on every profile (same arguments, thresholds and decisions bit-identical to it; the
+ *   thresholds into d_thr[F][S] unless NULL) and the cells above their threshold in ascending order in d_dets[F][cap], their
+ *   number in d_counts[F] -- exact also when a frame overflows cap, as in mmw_compact2d; entries past the count are not written.
+ *   S as far as mmw_range_profile_f64 serves it (and never beyond 49152: MMW_ERR_UNSUPPORTED), n_frames <= 65535.  MMW_ERR_INVALID (nothing launched): a null d_cubes / d_dets /
+ *   d_counts / ctx, n_frames outside [0, 65535], a non-positive shape, chirp_idx outside [-C, C), cap < 0, CFAR arguments
+ *   mmw_cfar1d refuses.  n_frames == 0: MMW_OK.  Profile family "range_detect" (the profile pass counts under its own). */
+int mmw_range_detect(mmw_ctx *ctx, const void *d_cubes, int n_frames, int V, int S, int C, int chirp_idx, int kind, int num_train,
+                     int num_guard, double scale, int k_rank, double *d_profile, double *d_thr, int32_t *d_dets,
+                     int32_t *d_counts, int cap);
 /* mmw_synth_array: the synthetic-array images of n_out frames of a resident batch, their windows read in place,
  *     d_out[i] = FFT_S( hann(S) . ( X_i[S][E] x W_i[E][T] ) ),   W_i[e][t] = hamming(E)[e] exp(j 2 pi d_t . p_{i,e} / lambda),
  *   Cv = ceil(C / k), E = H Cv, element e = (h, j) of X_i = d_cubes[h_frames[i] - H + 1 + h][v][s][j k]: the last H frames of

@@ -84,6 +84,8 @@ _SIGNATURES = {
     "mmw_dbs_gather": [_vp, _vp, _ip, _ip, _vp, _i, _i, _i, _i, _i],
     "mmw_dbs_sharpen": [_vp, _vp, _vp, _ip, _ip, _vp, _i, _i, _i, _i, _i, _ip, _i, _i],
     "mmw_micro_doppler": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
+    "mmw_sar_slices": [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _vp],
+    "mmw_range_detect": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _i],
     "mmw_synth_array": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ip, _i, C.POINTER(_d), C.POINTER(_d), _i, _d, _vp],
     "mmw_diag_synth_array_window": [_i, _i, _i, _i, _i, _i, _ip, _i, _ip],
     "mmw_synth_array_calibrate": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ip, _i, C.POINTER(_d), C.POINTER(_d), _i, _i, _d, _i, _vp, _vp,

@@ -618,6 +618,79 @@ class FramePipeline:
         d = self.micro_doppler_device(target_ranges, rx_idx)
         return d.download((self.n_frames, self.C), np.float32).astype(np.float64)
 
+    def strip_map_sar_device(self, proc, velocities, sensor_height_m: float = 0.24, rx_index: int = 0,
+                             max_SAR_distance: float = 1.5):
+        """The SAR slices of ``strip_map_sar`` left in HBM, nothing downloaded: ``(d_out, h_off, windows)`` -- the packed complex64
+        buffer, the int64 ``[n_frames + 1]`` element offsets of the frames' blocks in it and the int32 ``[n_frames, 4]`` windows
+        (row_lo, row_hi, col_lo, col_hi; half open).  Block f is row-major ``[row_hi - row_lo][col_hi - col_lo]``."""
+        from .processors.strip_map_SAR_processor import StripMapSARProcessor, frame_windows, sar_slices_call
+        # every argument check comes before the first use of self.ctx / self.bufs
+        if not isinstance(proc, StripMapSARProcessor):
+            raise ValueError(f"strip_map_sar: proc must be a StripMapSARProcessor, got {type(proc).__name__}")
+        F = self.n_frames
+        vel = np.asarray(velocities, dtype=np.float64)
+        if vel.ndim == 0:
+            vel = np.full(F, float(vel))
+        if vel.shape != (F,):
+            raise ValueError(f"strip_map_sar: velocities must be {F} numbers (one per resident frame) or one, got shape {vel.shape}")
+        rx = int(rx_index)
+        if not -self.V <= rx < self.V:
+            raise IndexError(f"strip_map_sar: rx_index {rx_index} is out of bounds for {self.V} antennas")
+        win, off = frame_windows(proc, vel, sensor_height_m, max_SAR_distance, self.S, self.C)
+        self.d_sar = self.bufs.get("sar_slices", max(int(off[-1]), 1) * 8)
+        sar_slices_call(self.ctx, self.d_in.ptr, F, self.V, self.S, self.C, rx % self.V, win, off, self.d_sar.ptr)
+        return self.d_sar, off, win
+
+    def strip_map_sar(self, proc, velocities, sensor_height_m: float = 0.24, rx_index: int = 0, max_SAR_distance: float = 1.5):
+        """``(slices, windows)``: entry f of the list ``slices`` is ``proc.process(cube_f, velocities[f], sensor_height_m, rx_index,
+        max_SAR_distance)`` of ``StripMapSARProcessor`` (reference: processors/strip_map_SAR_processor.py:160-194) -- complex128, the
+        shape of that frame's window, which moves with the frame's platform speed -- from one ``mmw_sar_slices`` call on the
+        resident (virtual-array) cubes and one download.  ``velocities`` is ``[n_frames]`` or one number for all frames;
+        ``windows`` is the int32 ``[n_frames, 4]`` table of ``strip_map_sar_device``.  Only ``proc``'s tables are read: its
+        ``valid_*_slice`` / mesh attributes stay what its last own call left (``proc.geometry(v)`` gives any frame's).  An
+        ``IndexError`` of the geometry (no range bin between height and distance) comes out as it does per frame."""
+        d, off, win = self.strip_map_sar_device(proc, velocities, sensor_height_m, rx_index, max_SAR_distance)
+        flat = d.download((int(off[-1]),), np.complex64).astype(np.complex128) if off[-1] else np.zeros(0, dtype=np.complex128)
+        return [flat[off[f]:off[f + 1]].reshape(win[f, 1] - win[f, 0], win[f, 3] - win[f, 2]) for f in range(len(win))], win
+
+    def range_detections(self, detector, chirp_idx: int = 0, return_thresholds: bool = False):
+        """Entry f of the returned list is ``RangeDetector.process(cube_f)`` of ``detector`` (reference:
+        processors/range_detector.py:59-83): the ascending int array of the range cells above their 1-D CFAR threshold on the
+        float64 range profile of chirp ``chirp_idx`` (the class uses chirp 0), from one ``mmw_range_detect`` call.
+        ``return_thresholds=True``: ``(dets, thresholds)`` with the float64 ``[n_frames, S]`` thresholds; ``self.range_profiles``
+        holds the float64 ``[n_frames, S]`` profiles either way.  Only the parameters of ``detector.cfar_detector`` are read.  A
+        detector the device cannot stand in for (a subclass, its own ``_compute_thresholds``) runs its own ``detect`` on each
+        downloaded profile instead."""
+        from .processors.range_detector import RangeDetector, device_cfar1d_args
+        # every argument check comes before the first use of self.ctx / self.bufs
+        if not isinstance(detector, RangeDetector):
+            raise ValueError(f"range_detections: detector must be a RangeDetector, got {type(detector).__name__}")
+        chirp = int(chirp_idx)
+        if not -self.C <= chirp < self.C:
+            raise IndexError(f"range_detections: chirp_idx {chirp_idx} is out of bounds for {self.C} chirps")
+        F, V, S, C = self.n_frames, self.V, self.S, self.C
+        args = device_cfar1d_args(detector.cfar_detector)
+        lib, h = self.ctx.lib, self.ctx.handle
+        d_prof = self.bufs.get("range_profile64", max(F, 1) * S * 8)
+        if args is None:
+            _lib.check(lib.mmw_range_profile_f64(h, self.d_in.ptr, d_prof.ptr, F, V, S, C, chirp))
+            self.range_profiles = d_prof.download((F, S), np.float64)
+            dets, thr = [], np.zeros((F, S))
+            for f in range(F):
+                dets.append(np.asarray(detector.cfar_detector.detect(self.range_profiles[f]), dtype=int))
+                thr[f] = detector.cfar_detector.thresholds
+            return (dets, thr) if return_thresholds else dets
+        kind, T, G, scale, k = args
+        d_thr = self.bufs.get("range_thr64", max(F, 1) * S * 8) if return_thresholds else None
+        d_dets, d_cnt = self.bufs.get("range_dets", max(F, 1) * S * 4), self.bufs.get("range_counts", max(F, 1) * 4)
+        _lib.check(lib.mmw_range_detect(h, self.d_in.ptr, F, V, S, C, chirp, kind, T, G, scale, k, d_prof.ptr,
+                                        d_thr.ptr if d_thr is not None else None, d_dets.ptr, d_cnt.ptr, S))
+        self.range_profiles = d_prof.download((F, S), np.float64)
+        counts = d_cnt.download((F,), np.int32)
+        table = d_dets.download((F, S), np.int32)
+        dets = [table[f, :counts[f]].astype(int) for f in range(F)]
+        return (dets, d_thr.download((F, S), np.float64)) if return_thresholds else dets
+
     def capon_range_angle_device(self, thetas_rad, rx_antennas, range_bins=None, delta: float = 1e-3,
                                  perform_windowing: bool = True, frames_per_pass: Optional[int] = None) -> _lib.DeviceBuffer:
         """The Capon maps of ``capon_range_angle`` left in HBM: float32 ``[n_frames][R_w][T]``, nothing downloaded."""
@@ -1678,6 +1751,29 @@ class MultiDeviceFramePipeline:
         ``micro_doppler_history`` of the result is the spectrogram)."""
         rows = self._join(self._each(lambda r: self.parts[r].micro_doppler(target_ranges, rx_idx)))
         return np.asarray(rows, dtype=np.float64).reshape(self.n_frames, self.shape[2])
+
+    def strip_map_sar(self, proc, velocities, sensor_height_m: float = 0.24, rx_index: int = 0, max_SAR_distance: float = 1.5):
+        """``FramePipeline.strip_map_sar`` of every shard on its rows of ``velocities``, joined in frame order (a frame's slice
+        depends on that frame alone): ``(slices, windows)``."""
+        vel = np.asarray(velocities, dtype=np.float64)
+        if vel.ndim == 0:
+            vel = np.full(self.n_frames, float(vel))
+        if vel.shape != (self.n_frames,):
+            raise ValueError(f"strip_map_sar: velocities must be {self.n_frames} numbers or one, got shape {vel.shape}")
+        per_rank = self._each(lambda r: self.parts[r].strip_map_sar(proc, vel[self.bounds[r][0]:self.bounds[r][1]], sensor_height_m,
+                                                                   rx_index, max_SAR_distance))
+        slices = self._join([p[0] for p in per_rank])
+        wins = [np.asarray(p[1], dtype=np.int32).reshape(-1, 4) for p in per_rank]
+        return slices, (np.concatenate(wins) if wins else np.zeros((0, 4), dtype=np.int32))
+
+    def range_detections(self, detector, chirp_idx: int = 0, return_thresholds: bool = False):
+        """``FramePipeline.range_detections`` of every shard, joined in frame order (the detector keeps no state across frames)."""
+        per_rank = self._each(lambda r: self.parts[r].range_detections(detector, chirp_idx, return_thresholds))
+        if not return_thresholds:               # no shard writes or downloads a threshold table nobody asked for
+            return self._join(per_rank)
+        dets = self._join([p[0] for p in per_rank])
+        thr = [np.asarray(p[1], dtype=np.float64).reshape(-1, self.shape[1]) for p in per_rank]
+        return dets, (np.concatenate(thr) if thr else np.zeros((0, self.shape[1])))
 
     def capon_range_angle(self, thetas_rad, rx_antennas, range_bins=None, delta: float = 1e-3, perform_windowing: bool = True,
                           frames_per_pass: Optional[int] = None) -> np.ndarray:

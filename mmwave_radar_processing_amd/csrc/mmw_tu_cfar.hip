@@ -1,9 +1,10 @@
-// Translation unit of the CFAR entry points (mmw_cfar.h), the batched ground detector (mmw_ground.h) and the batched sequential
-// detector (mmw_seq.h).
+// Translation unit of the CFAR entry points (mmw_cfar.h), the batched ground detector (mmw_ground.h), the batched sequential
+// detector (mmw_seq.h) and the batched range detector (mmw_range_detect.h).
 #include "mmw_entry.h"
 #include "mmw_cfar.h"
 #include "mmw_ground.h"
 #include "mmw_seq.h"
+#include "mmw_range_detect.h"
 
 #include <algorithm>
 
@@ -111,7 +112,43 @@ static int cfar1d_args_ok(int kind, int num_train, int num_guard, int k_rank) {
     return MMW_OK;
 }
 
+// Every argument of mmw_range_detect is judged here, before the context is touched: the function is not given the context, so a
+// refused call cannot enqueue anything and needs no device (tests/cpp/sar_range_sanitize.cpp relies on it).
+static int range_detect_validate(bool have_ctx, const void *d_cubes, int n_frames, int V, int S, int C, int chirp_idx, int kind,
+                                 int num_train, int num_guard, int k_rank, const void *d_dets, const void *d_counts, int cap) {
+    MMW_REQUIRE(have_ctx && d_cubes && d_dets && d_counts, "null argument (ctx %d, d_cubes %d, d_dets %d, d_counts %d)", (int)have_ctx,
+                d_cubes != nullptr, d_dets != nullptr, d_counts != nullptr);
+    MMW_REQUIRE(n_frames >= 0 && n_frames <= 65535, "n_frames is %d (0 to 65535 per call)", n_frames);
+    MMW_REQUIRE(V > 0 && S > 0 && C > 0, "bad shape: V %d, S %d, C %d must all be positive", V, S, C);
+    MMW_REQUIRE(chirp_idx >= -C && chirp_idx < C, "chirp_idx %d is not a chirp of [-%d, %d)", chirp_idx, C, C);
+    MMW_REQUIRE(cap >= 0, "cap is %d", cap);
+    return cfar1d_args_ok(kind, num_train, num_guard, k_rank);
+}
+
 extern "C" {
+
+int mmw_range_detect(mmw_ctx *ctx, const void *d_cubes, int n_frames, int V, int S, int C, int chirp_idx, int kind, int num_train,
+                     int num_guard, double scale, int k_rank, double *d_profile, double *d_thr, int32_t *d_dets, int32_t *d_counts,
+                     int cap) {
+    MMW_TRY(range_detect_validate(ctx != nullptr, d_cubes, n_frames, V, S, C, chirp_idx, kind, num_train, num_guard, k_rank, d_dets,
+                                  d_counts, cap));
+    if (S > RANGE_DETECT_MAX_S)
+        return set_error(MMW_ERR_UNSUPPORTED, "range detector: %d range cells, at most %d (one flag byte per cell in the LDS)", S,
+                         RANGE_DETECT_MAX_S);
+    if (n_frames == 0) return MMW_OK;
+    // the profile pass works in the head of the scratch; a profile nobody asked for goes behind it
+    const size_t head = ((size_t)n_frames * V * S * 2 * sizeof(double) + 255) & ~(size_t)255;
+    if (!d_profile) {
+        MMW_JOIN(ctx);
+        MMW_TRY(ensure_scratch(ctx, head + (size_t)n_frames * S * sizeof(double)));
+        d_profile = (double *)((char *)ctx->scratch + head);
+    }
+    MMW_TRY(range_profile_impl<double>(ctx, d_cubes, d_profile, n_frames, V, S, C, chirp_idx));
+    Cfar1dArgs a{d_profile, d_thr, nullptr, nullptr, n_frames, S, kind, num_train, num_guard, scale, k_rank};
+    ProfScope ps(ctx, "range_detect");
+    hipLaunchKernelGGL(k_range_detect, dim3(n_frames), dim3(256), (size_t)S, ctx->stream, a, d_dets, d_counts, cap);
+    return check_launch("range_detect");
+}
 
 int mmw_cfar2d(mmw_ctx *ctx, const double *d_X, double *d_thr, double *d_noise, uint8_t *d_mask, int n_frames,
                int R, int D, int kind, int train_r, int train_d, int guard_r, int guard_d, double scale,

@@ -8,8 +8,11 @@ from .range_angle_resp_dbs_enhanced import RangeAngleProcessorDBSEnhanced
 from .point_cloud_generator import PointCloudGenerator
 from .doppler_azimuth_resp import DopplerAzimuthProcessor
 from .micro_doppler_resp import MicroDopplerProcessor
+from .strip_map_SAR_processor import StripMapSARProcessor
+from .range_detector import RangeDetector
 from .synthetic_array_beamformer import SelfCalibratingSyntheticArrayProcessor, SyntheticArrayBeamformerProcessor
 
 __all__ = ["_Processor", "VirtualArrayReformatter", "RangeProcessor", "Altimeter", "RangeDopplerProcessor",
            "RangeAngleProcessor", "RangeAngleProcessorDBSEnhanced", "PointCloudGenerator", "DopplerAzimuthProcessor",
-           "MicroDopplerProcessor", "SyntheticArrayBeamformerProcessor", "SelfCalibratingSyntheticArrayProcessor"]
+           "MicroDopplerProcessor", "SyntheticArrayBeamformerProcessor", "SelfCalibratingSyntheticArrayProcessor",
+           "StripMapSARProcessor", "RangeDetector"]
