@@ -518,6 +518,35 @@ int mmw_ego_velocity_ransac(mmw_ctx *ctx, const double *d_points, const int32_t 
                             const int32_t *d_trials_tab, int tab_len, const int32_t *d_trials_off, double *d_out,
                             int32_t *d_flags, uint8_t *d_inlier_mask);
 
+/* mmw_vehicle_velocity_ransac: VehicleVelEstimator.estimate_ego_vel (point_cloud_processing/vehicle_vel_estimator.py) for every
+ *   frame of d_points[F][cap][4] / d_counts[F] (the buffers of mmw_ego_velocity_ransac), dim 2 or 3 (only_2D or not).  Per frame:
+ *   H = p[:dim] / |p[:dim]|, y = v (no sign change); with an initial estimate the points with (v - H . (-init))^2 <
+ *   static_vel_thresh are kept, in order; N of them: below num_close_pts the result is empty.  Iteration i of max_iters fits the
+ *   points d_draws[N - points_per_fit][i][0 .. points_per_fit) (the caller's first entries of the i-th rng.permutation(N)) by
+ *   dim x dim normal equations, adds every other point whose squared residual is below fit_thresh, and with more than
+ *   num_close_pts members refits on all of them; the smallest mean squared error wins, the lowest iteration among equals.
+ *   d_init: NULL, or [F][dim] with a NaN in the rows that have no estimate.  chain != 0: d_init is NULL or one row [1][dim], and
+ *   ONE workgroup walks the frames in order, every frame taking the last estimate found before it (or the seed row) as its
+ *   initial estimate.
+ *   d_out[F][dim + 2]: the ego velocity (minus the fit), the mean squared error, N.  d_status[F]: 1 an estimate, 0 the empty
+ *   result (d_out holds zeros and N).  d_flags[F]: 0, or MMW_VEHICLE_FLAG_* bits: a decision of the frame lies within rounding of
+ *   the host class's, its d_out row is zero, its status 0, and the caller recomputes it.  A flagged frame ends a chain: the frames
+ *   behind it carry MMW_VEHICLE_FLAG_CHAIN alone, and the caller goes on from them with the recomputed estimate as the seed.
+ *   n_tab: rows of d_draws; a frame whose N has no row, or a row with an entry that is no index below N or is repeated, is
+ *   flagged.  LDS: 4 cap + 9 max_iters + 192 doubles; MMW_ERR_UNSUPPORTED beyond 160 KiB.  Every argument is judged before the
+ *   context is touched; n_frames == 0 launches nothing. */
+#define MMW_VEHICLE_FLAG_RESIDUAL 1    /* a squared residual within the band of fit_thresh */
+#define MMW_VEHICLE_FLAG_STATIC 2      /* a squared residual of the static filter within the band of static_vel_thresh */
+#define MMW_VEHICLE_FLAG_ERROR_TIE 4   /* an error within the bands of the smallest one, from different members */
+#define MMW_VEHICLE_FLAG_COND 8        /* a Gram matrix beyond the condition cap 1e6, or not positive definite */
+#define MMW_VEHICLE_FLAG_NONFINITE 16  /* a non-finite point, a point at range 0, an infinite initial estimate */
+#define MMW_VEHICLE_FLAG_TABLES 32     /* the draw table does not serve N (caller error; nothing computed) */
+#define MMW_VEHICLE_FLAG_CHAIN 64      /* not reached: an earlier frame of the chain was flagged */
+int mmw_vehicle_velocity_ransac(mmw_ctx *ctx, const double *d_points, const int32_t *d_counts, int n_frames, int cap, int dim,
+                                int points_per_fit, int max_iters, double fit_thresh, int num_close_pts, double static_vel_thresh,
+                                const double *d_init, const int32_t *d_draws, int n_tab, int chain, double *d_out, int32_t *d_status,
+                                int32_t *d_flags);
+
 /* mmw_detect_batch: the detection pipeline of RangeDopplerDetector2D for a batch of frames in one call:
  *   d_rd[F][V][S][C] c64 (mmw_range_doppler) and, for antenna 0, d_mag64[F][S][C] -> 2-D CFAR mask -> ordered
  *   detections d_dets[F][cap][2] / d_counts[F]

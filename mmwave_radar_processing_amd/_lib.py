@@ -35,6 +35,9 @@ DOPAZ_FLAG_RESIDUAL, DOPAZ_FLAG_SCORE_TIE, DOPAZ_FLAG_R2, DOPAZ_FLAG_SHARE = 1, 
 DOPAZ_FLAG_A_ZERO, DOPAZ_FLAG_NONFINITE, DOPAZ_FLAG_UNDECIDED, DOPAZ_FLAG_TABLES = 16, 32, 64, 128
 DOPAZ_FLAG_MASK, DOPAZ_STATUS_SHIFT, DOPAZ_STATUS_MASK, DOPAZ_INLIERS_SHIFT = 0xff, 8, 3, 16
 DOPAZ_STATUS_OK, DOPAZ_STATUS_EMPTY, DOPAZ_STATUS_FAILED = 0, 1, 2
+# include/mmwgpu.h MMW_VEHICLE_FLAG_*: the flag word of mmw_vehicle_velocity_ransac
+VEHICLE_FLAG_RESIDUAL, VEHICLE_FLAG_STATIC, VEHICLE_FLAG_ERROR_TIE, VEHICLE_FLAG_COND = 1, 2, 4, 8
+VEHICLE_FLAG_NONFINITE, VEHICLE_FLAG_TABLES, VEHICLE_FLAG_CHAIN = 16, 32, 64
 
 
 class MmwGpuError(RuntimeError):
@@ -119,6 +122,7 @@ _SIGNATURES = {
     "mmw_seq_route": [_vp, _i, _i],
     "mmw_point_cloud": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i],
     "mmw_ego_velocity_ransac": [_vp, _vp, _vp, _i, _i, _i, _d, _d, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp],
+    "mmw_vehicle_velocity_ransac": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _d, _vp, _vp, _i, _i, _vp, _vp, _vp],
     "mmw_detect_points_supported": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i],
     "mmw_detect_points": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i,
                           _ip, _i, _i, _ip, _i, _i, _i, _ip],

@@ -1558,6 +1558,129 @@ class FramePipeline:
         fits, counts = self.ego_fits(estimator, point_clouds)
         return ego_state_scan(estimator, fits, counts)
 
+    # ------------------------------------------------------------------ vehicle velocity RANSAC
+    def vehicle_fits(self, estimator, point_clouds: Optional[Sequence[np.ndarray]] = None, initial=None, track: bool = False,
+                     only_2D: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """``estimator.estimate_ego_vel`` (a ``VehicleVelEstimator``) for every frame (``mmw_vehicle_velocity_ransac``): float64
+        ``[F, dim + 2]`` rows (ego velocity, mean squared error of the winning refit, points behind the static filter) and int32
+        ``status [F]`` (1: an estimate; 0: the class's empty array, the row's velocity and error zero), dim = 2 for ``only_2D``.
+        Point clouds: those of ``point_clouds_device()``, or the caller's ``point_clouds`` (``(N, 4)`` arrays).  ``initial``: None,
+        or ``[F, dim]`` previous estimates for the static filter, a NaN row for a frame that has none.  ``track=True``: the
+        frames form one drive -- each takes the last estimate found before it as its initial estimate (``initial``: None or
+        the ``[dim]`` estimate before the first frame) -- which runs as ONE workgroup walking the frames in order.  Frames the
+        kernel flags (``vehicle_flags``, ``n_vehicle_flagged``: a decision within rounding of the host class's) are recomputed by
+        the estimator's host path with the same draws; a chain goes on behind such a frame from the recomputed estimate.  The
+        draws' seed is ``estimator.seed``, or, when that is None, one drawn from OS entropy for this call (``vehicle_seed``).
+        The estimator itself is left untouched."""
+        import copy
+        import os
+        from .point_cloud_processing import ransac_tables as T
+        dim = 2 if only_2D else 3
+        ppf, iters, ncp = int(estimator.points_per_fit), int(estimator.max_iters), int(estimator.num_close_pts)
+        n_init = None if point_clouds is None else len(point_clouds)
+        F_known = self.n_frames if n_init is None else n_init
+        init = None
+        if initial is not None:
+            init = np.ascontiguousarray(initial, dtype=np.float64)
+            want = (dim,) if track else (F_known, dim)
+            if init.shape != want:
+                raise ValueError(f"vehicle_fits: initial must have shape {want}{' with track=True' if track else ''}, got {init.shape}")
+        if point_clouds is None:
+            self.point_clouds_device()
+            F, counts = self.n_frames, np.asarray(self.counts)
+        else:
+            F, counts = self._upload_points(point_clouds)
+        cap, bufs, F1 = self.cap, self.bufs, max(F, 1)
+        seed = estimator.seed if estimator.seed is not None else int.from_bytes(os.urandom(8), "little")
+        self.vehicle_seed = seed
+        live = counts[counts >= ncp]
+        n_max = int(live.max()) if live.size else 0
+        filtered = track or (init is not None and not np.isnan(init).any(axis=-1).all())
+        draws = T.vehicle_tables(seed, range(ncp, n_max + 1) if filtered else live.tolist(), n_max, iters, ppf)
+        d_draws = bufs.get("vehicle_draws", draws.nbytes)
+        d_draws.upload(draws)
+        d_out, d_status, d_flags = (bufs.get("vehicle_out", F1 * (dim + 2) * 8), bufs.get("vehicle_status", F1 * 4),
+                                    bufs.get("vehicle_flags", F1 * 4))
+        d_init = bufs.get("vehicle_init", F1 * dim * 8)
+        host = copy.copy(estimator)
+
+        def launch(f0, n, has_init, chain):
+            _lib.check(self.ctx.lib.mmw_vehicle_velocity_ransac(
+                self.ctx.handle, self.d_points.at(f0 * cap * 32), self._points_cnt.at(f0 * 4), n, cap, dim, ppf, iters,
+                float(estimator.fit_thresh), ncp, float(estimator.static_vel_thresh), d_init.ptr if has_init else None, d_draws.ptr,
+                len(draws), int(chain), d_out.at(f0 * (dim + 2) * 8), d_status.at(f0 * 4), d_flags.at(f0 * 4)))
+
+        def fetch(f0, n):
+            return (d_out.download((n, dim + 2), np.float64, f0 * (dim + 2) * 8).copy(),
+                    d_status.download((n,), np.int32, f0 * 4).copy(), d_flags.download((n,), np.int32, f0 * 4).copy())
+
+        def on_host(f, prior):
+            """Frame f by the estimator's host path: its row and status."""
+            pts = self.d_points.download((int(counts[f]), 4), np.float64, f * cap * 32) if counts[f] else np.empty((0, 4))
+            have = prior is not None and not np.isnan(prior).any()
+            found, kept = host.ransac(pts, prior if have else np.empty(0), only_2D, seed=seed)
+            row = np.zeros(dim + 2)
+            if found:
+                row[:dim], row[dim] = host.get_vehicle_vel_est(), host.best_error
+            row[dim + 1] = kept
+            return row, int(found)
+
+        if not track:
+            if init is not None and F:
+                d_init.upload(init)
+            launch(0, F, init is not None, False)
+            fits, status, flags = fetch(0, F) if F else (np.zeros((0, dim + 2)), np.zeros(0, np.int32), np.zeros(0, np.int32))
+            for f in np.nonzero(flags)[0].tolist():
+                fits[f], status[f] = on_host(f, None if init is None else init[f])
+        else:
+            fits, status, flags = np.zeros((F, dim + 2)), np.zeros(F, dtype=np.int32), np.zeros(F, dtype=np.int32)
+            carry = None if init is None or np.isnan(init).any() else init.copy()
+            f0 = 0
+            while f0 < F:
+                if carry is not None:
+                    d_init.upload(carry)
+                launch(f0, F - f0, carry is not None, True)
+                out, st, fl = fetch(f0, F - f0)
+                stop = int(np.nonzero(fl)[0][0]) if fl.any() else F - f0
+                fits[f0:f0 + stop], status[f0:f0 + stop] = out[:stop], st[:stop]
+                found = np.nonzero(st[:stop])[0]
+                if len(found):
+                    carry = out[found[-1], :dim].copy()
+                f0 += stop
+                if f0 < F:                      # the frame that ended the chain: the host decides it, the chain goes on behind it
+                    flags[f0] = fl[stop]
+                    fits[f0], status[f0] = on_host(f0, carry)
+                    if status[f0]:
+                        carry = fits[f0, :dim].copy()
+                    f0 += 1
+        self.vehicle_flags = flags
+        self.n_vehicle_flagged = int(np.count_nonzero(flags))
+        return fits, status
+
+    def vehicle_velocities(self, estimator, point_clouds: Optional[Sequence[np.ndarray]] = None, initial=None, track: bool = False,
+                           only_2D: bool = True) -> np.ndarray:
+        """``estimator.estimate_ego_vel`` on every frame in order (``vehicle_fits``): float64 ``[F, dim]``, a NaN row where the
+        class returns the empty array.  ``estimator.best_fit`` and ``estimator.best_error`` are left as the frame loop leaves them."""
+        fits, status = self.vehicle_fits(estimator, point_clouds, initial, track, only_2D)
+        return vehicle_state_scan(estimator, fits, status)
+
+
+def vehicle_state_scan(estimator, fits: np.ndarray, status: np.ndarray) -> np.ndarray:
+    """The ``[F, dim]`` estimates (NaN rows: none) of ``vehicle_fits``' rows, and the state ``VehicleVelEstimator.estimate_ego_vel``
+    leaves behind frame by frame: nothing changes below ``num_close_pts`` points, the error is reset to inf from there on, and a
+    found estimate installs its fit (minus the velocity) and its error."""
+    dim = fits.shape[1] - 2
+    out = np.full((len(fits), dim), np.nan)
+    for f in range(len(fits)):
+        if fits[f, dim + 1] < estimator.num_close_pts:
+            continue
+        if status[f]:
+            out[f] = fits[f, :dim]
+            estimator.best_fit, estimator.best_error = -1 * fits[f, :dim], float(fits[f, dim])
+        else:
+            estimator.best_error = np.inf
+    return out
+
 
 def ego_state_scan(estimator, fits: np.ndarray, counts: Sequence[int]) -> np.ndarray:
     """``VelocityEstimator.process`` for every frame given the frames' fits (``[F, dim + 2]``) and point counts: an empty frame
@@ -1725,6 +1848,36 @@ class MultiDeviceFramePipeline:
             raise RuntimeError(f"joined {len(counts)} per-frame fits for {self.n_frames} frames")
         self.n_ego_flagged = sum(getattr(self.parts[r], "n_ego_flagged", 0) for r in live)
         return ego_state_scan(estimator, fits, counts)
+
+    def vehicle_velocities(self, estimator, initial=None, track: bool = False, only_2D: bool = True) -> np.ndarray:
+        """``FramePipeline.vehicle_velocities`` for independent frames: every device fits the frames of its shard
+        (``vehicle_fits`` with its rows of ``initial``, all from one seed: ``vehicle_seed``), the estimator's state runs once over
+        the joined fits in frame order.  ``track=True`` is refused: a chain hands every frame's estimate to the next one, so it
+        cannot be split by frames -- use one ``FramePipeline``."""
+        import copy
+        import os
+        if track:
+            raise ValueError("MultiDeviceFramePipeline.vehicle_velocities cannot take track=True: the chain runs through the "
+                             "frames in order, so it cannot be split across devices -- use one FramePipeline")
+        dim = 2 if only_2D else 3
+        init = None
+        if initial is not None:
+            init = np.asarray(initial, dtype=np.float64)
+            if init.shape != (self.n_frames, dim):
+                raise ValueError(f"vehicle_velocities: initial must have shape {(self.n_frames, dim)}, got {init.shape}")
+        est = copy.copy(estimator)
+        if est.seed is None:
+            est.seed = int.from_bytes(os.urandom(8), "little")
+        self.vehicle_seed = est.seed
+        live = [r for r in range(self.world) if self.bounds[r][1] > self.bounds[r][0]]
+        per_rank = self._each(lambda r: self.parts[r].vehicle_fits(
+            est, None, None if init is None else init[self.bounds[r][0]:self.bounds[r][1]], False, only_2D))
+        fits = np.concatenate([f for f, _ in per_rank]) if per_rank else np.zeros((0, dim + 2))
+        status = np.concatenate([s for _, s in per_rank]) if per_rank else np.zeros(0, dtype=np.int32)
+        if len(fits) != self.n_frames:
+            raise RuntimeError(f"joined {len(fits)} per-frame fits for {self.n_frames} frames")
+        self.n_vehicle_flagged = sum(getattr(self.parts[r], "n_vehicle_flagged", 0) for r in live)
+        return vehicle_state_scan(estimator, fits, status)
 
     def doppler_azimuth_velocities(self, estimator, altitudes, enable_precise_responses=False) -> np.ndarray:
         """``FramePipeline.doppler_azimuth_velocities``: every device fits the frames of its shard (``doppler_azimuth_fits`` with

@@ -6,6 +6,9 @@ here once per N (and kept for the life of the process) and the kernel only looks
 * ``subset_table(N)``: the 20 x 10 indices ``RANSACRegressor(random_state=42, min_samples=10, max_trials=20).fit`` draws for N
   samples -- a fresh ``RandomState(42)`` per fit, one ``sample_without_replacement(N, 10)`` per trial, skipped or not;
 * ``trials_table(N)``: ``min(20, _dynamic_max_trials(k, N, 10, 0.99))`` for k = 0 .. N inliers.
+
+``vehicle_draws`` / ``vehicle_tables`` do the same for ``VehicleVelEstimator``'s own loop (``mmw_vehicle_velocity_ransac``,
+DESIGN.md 4.25): the heads of ``default_rng(seed).permutation(N)``, NumPy only.
 """
 from __future__ import annotations
 
@@ -126,3 +129,40 @@ def dopaz_tables(n_rows: int) -> Tuple[np.ndarray, np.ndarray]:
             t.setflags(write=False)
         _dopaz[n_rows] = tabs
     return tabs
+
+
+_vehicle: Dict[Tuple[int, int, int, int], np.ndarray] = {}
+VEHICLE_CACHE_TABLES = 4096      # draw tables kept (an unseeded estimator's batch calls bring a new seed each): emptied beyond that
+
+
+def vehicle_draws(seed, n: int, max_iters: int, points_per_fit: int) -> np.ndarray:
+    """The draws of one ``VehicleVelEstimator.estimate_ego_vel`` call on ``n`` points: int32 ``[max_iters, points_per_fit]``, row i
+    the first ``points_per_fit`` entries of the i-th ``rng.permutation(n)`` of a fresh ``np.random.default_rng(seed)`` (the rest of
+    a permutation only orders the class's sums).  Kept per ``(seed, n, max_iters, points_per_fit)``, at most ``VEHICLE_CACHE_TABLES`` of them; ``seed=None`` draws from OS
+    entropy and keeps nothing.  The host class and ``mmw_vehicle_velocity_ransac``'s tables both come from here."""
+    n, max_iters, points_per_fit = int(n), int(max_iters), int(points_per_fit)
+    if n < points_per_fit:
+        raise ValueError(f"no {points_per_fit}-point draw from {n} points")
+    key = None if seed is None else (int(seed), n, max_iters, points_per_fit)
+    tab = _vehicle.get(key) if key is not None else None
+    if tab is None:
+        rng = np.random.default_rng(seed)
+        tab = np.array([rng.permutation(n)[:points_per_fit] for _ in range(max_iters)], dtype=np.int32).reshape(max_iters, points_per_fit)
+        tab.setflags(write=False)
+        if key is not None:
+            if len(_vehicle) >= VEHICLE_CACHE_TABLES:
+                _vehicle.clear()
+            _vehicle[key] = tab
+    return tab
+
+
+def vehicle_tables(seed, sizes, n_max: int, max_iters: int, points_per_fit: int) -> np.ndarray:
+    """The ``d_draws`` argument of ``mmw_vehicle_velocity_ransac``: int32 ``[n_tab, max_iters, points_per_fit]`` with row
+    ``N - points_per_fit`` the draws for N points, ``n_tab = n_max - points_per_fit + 1`` (one unused row when that is below 1).
+    Only the point counts in ``sizes`` are drawn; every other row holds -1, which the kernel reports instead of reading."""
+    n_tab = max(int(n_max) - int(points_per_fit) + 1, 1)
+    tab = np.full((n_tab, int(max_iters), int(points_per_fit)), -1, dtype=np.int32)
+    for n in sorted({int(n) for n in sizes}):
+        if points_per_fit <= n <= n_max:
+            tab[n - points_per_fit] = vehicle_draws(seed, n, max_iters, points_per_fit)
+    return tab
