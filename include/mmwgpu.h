@@ -264,6 +264,24 @@ int mmw_synth_array_calibrate(mmw_ctx *ctx, const void *d_cubes, int n_resident,
 int mmw_diag_synth_array_calib_host(const double *h_avg, const double *h_avg_err, int S, const double *h_mag, double mag_band, int n_az,
                                     int n_el, const double *h_Fq, const double *h_l1, int E, const double *h_P, const double *h_dirs,
                                     double lambda_m, double *h_Pcal, int32_t *h_targets, int32_t info[4]);
+/* mmw_synth_array_pattern: the beam patterns (array factors) of n synthetic-array geometries, no taper and no data (DESIGN.md 4.26,
+ *   mmw_synth_pattern.h; SyntheticArrayBeamformerProcessor.compute_synthetic_array_pattern,
+ *   processors/simple_synthetic_array_beamformer_processor_multiFrame.py:615-670):
+ *     AF_i[t] = sum_e exp(j 2 pi d_t . p_{i,e} / lambda) in float64,  a_i[t] = float32(|AF_i[t]|),  pattern_i[t] = a_i[t] / max_t a_i[t]
+ *   with the division and the maximum in float32.  d_P [n][3][E] DEVICE float64 -- the layout of mmw_synth_array's h_P, and of the
+ *   d_Pcal mmw_synth_array_calibrate leaves behind, which is read in place; h_dirs [3][T] HOST float64, free again when the call
+ *   returns; d_pattern [n][T] float32; d_af [n][T] complex128, the un-normalised AF, or NULL.  The phase is reduced in cycles before
+ *   the sine and cosine and the summation order is fixed: a call repeats bit for bit.  A frame with a non-finite coordinate gives
+ *   an all-NaN pattern (as numpy), the other frames are unaffected; 0 / 0 is what IEEE makes it.  The normalisation is enqueued
+ *   behind the magnitudes, no host synchronisation.
+ *   MMW_ERR_INVALID (nothing enqueued, outputs untouched): a null ctx / d_P / h_dirs / d_pattern, n < 0, E < 1, T < 1, lambda_m
+ *   not finite or <= 0, n T or 3 n E beyond int32.  n == 0: MMW_OK, nothing launched.  Profile family "synth_pattern".
+ * mmw_diag_synth_array_pattern_host: the same accumulation (one implementation, mmw_synth_pattern.h) on host pointers; no context,
+ *   no device. */
+int mmw_synth_array_pattern(mmw_ctx *ctx, const double *d_P, int n, int E, const double *h_dirs, int T, double lambda_m,
+                            float *d_pattern, void *d_af);
+int mmw_diag_synth_array_pattern_host(const double *h_P, int n, int E, const double *h_dirs, int T, double lambda_m,
+                                      float *h_pattern, void *h_af);
 /* mmw_mean_over_range: d_out[F][C][A] float32 = mean over range rows [s_lo, s_hi) of d_mag[F][A][S][C];
  *   with mmw_chain3d(flags | MAGNITUDE) this is DopplerAzimuthProcessor.process, coarse path
  *   (processors/doppler_azimuth_resp.py:84-128,296-334,419-491): range FFT -> range-window mask ->

@@ -94,6 +94,8 @@ _SIGNATURES = {
     "mmw_synth_array_calibrate": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ip, _i, C.POINTER(_d), C.POINTER(_d), _i, _i, _d, _i, _vp, _vp,
                                   _vp, _vp],
     "mmw_diag_synth_array_calib_host": [_vp, _vp, _i, _vp, _d, _i, _i, _vp, _vp, _i, _vp, _vp, _d, _vp, _vp, _vp],
+    "mmw_synth_array_pattern": [_vp, _vp, _i, _i, C.POINTER(_d), _i, _d, _vp, _vp],
+    "mmw_diag_synth_array_pattern_host": [_vp, _i, _i, _vp, _i, _d, _vp, _vp],
     "mmw_mean_over_range": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i],
     "mmw_doppler_azimuth": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i],
     "mmw_doppler_azimuth_zoom": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_d), _i, _i],

@@ -17,8 +17,9 @@ from . import _lib
 from .detectors.base import BaseCFAR1D
 from .detectors.ca_cfar import CaCFAR2D
 from .processors.range_angle_resp import angle_tables
-from .processors.steering_beamformers import (CAPON_PASS_BUDGET, capon_cube_args, capon_from_cubes,  # noqa: F401
-                                              capon_pass_frames, capon_passes)
+from .processors.steering_beamformers import (CAPON_PASS_BUDGET, array_pattern_args, array_patterns,  # noqa: F401
+                                              array_patterns_on, capon_cube_args, capon_from_cubes, capon_pass_frames,
+                                              capon_passes)
 
 
 def shard_bounds(n_frames: int, rank: int, world: int) -> Tuple[int, int]:
@@ -204,6 +205,15 @@ def synthetic_array_geometry(proc, velocities) -> Tuple[np.ndarray, np.ndarray]:
     return valid, (np.stack(geoms) if geoms else np.zeros((0, 3, E)))
 
 
+def synthetic_array_patterns(proc, velocities, ctx: _lib.Context = None) -> Tuple[np.ndarray, np.ndarray]:
+    """``(frames, patterns)``: the beam pattern float32 ``[n_valid, n_az, n_el]`` that ``proc.compute_synthetic_array_pattern(
+    proc.array_geometry)`` gives after each frame whose geometry is valid when a fresh processor like ``proc`` is stepped through
+    ``velocities [n, 3]`` -- frames and geometries are those of ``synthetic_array_geometry``, all patterns one
+    ``mmw_synth_array_pattern`` call.  No cubes are involved, so ``n`` may be a whole drive.  ``proc`` is only read."""
+    valid, P = synthetic_array_geometry(proc, velocities)
+    return np.flatnonzero(valid).astype(np.int64), array_patterns(P, proc.d, proc.lambda_m, ctx=ctx)
+
+
 def _per_frame_pairs(what: str, pairs, n_frames: Optional[int]) -> np.ndarray:
     """``[F][2]`` float64 copy of one pair for all frames or of one pair per frame."""
     arr = np.array(pairs, dtype=np.float64)
@@ -351,6 +361,17 @@ class FramePipeline:
         _, self.angle_bins = angle_tables(self.A)
         self.cube_bytes = self.V * self.S * self.C * 8
         self.d_in = self.bufs.get("cubes", self.max_frames * self.cube_bytes)
+
+    # Every way frames become resident (load*, synth, a stream() chunk) ends by setting n_frames: what is remembered about results
+    # computed from the cubes before -- the arguments of the last calibration, for synthetic_array_patterns -- is forgotten there.
+    @property
+    def n_frames(self):
+        return self._n_frames
+
+    @n_frames.setter
+    def n_frames(self, n):
+        self._n_frames = n
+        self._synth_calib_key = None
 
     # ------------------------------------------------------------------ input
     def load(self, cubes: np.ndarray):
@@ -1104,6 +1125,7 @@ class FramePipeline:
         v, frames, P, dirs, n_az, n_el = self._synthetic_array_arguments(proc, velocities, "synthetic_array_calibrated")
         T, H, k, n = n_az * n_el, int(proc.num_frames), int(proc.stride), len(frames)
         E, lam = P.shape[2], float(proc.lambda_m)
+        self._synth_calib_key = None
         self.d_synth = self.bufs.get("synth_array", max(n, 1) * self.S * T * 8)
         d_P = self.bufs.get("synth_calib_P", max(n, 1) * 3 * E * 8)
         d_st = self.bufs.get("synth_calib_status", max(n, 1) * 4)
@@ -1173,6 +1195,9 @@ class FramePipeline:
             for j, q in enumerate(flagged):
                 self.d_synth.upload(out[j], byte_offset=int(q) * self.S * T * 8)
         self.synth_geometry_calibrated, self.synth_calib_status, self.synth_calib_targets = Pcal, status, targets
+        # for synthetic_array_patterns(calibrated=True): what was calibrated, and the rows of d_P the host route has since corrected
+        self._synth_calib_key = (v, k, H, lam, n_it, n_az, n_el, frames, P, dirs)
+        self._synth_calib_stale = [int(q) for q in flagged]
         return frames.astype(np.int64), self.d_synth
 
     def synthetic_array_calibrated(self, proc, velocities, num_calibration_iters: int = 1) -> Tuple[np.ndarray, np.ndarray]:
@@ -1187,6 +1212,55 @@ class FramePipeline:
         n_az, n_el = np.shape(proc.d)[1:]
         out = d.download((len(frames), self.S, n_az * n_el), np.complex64) if len(frames) else np.zeros((0, self.S, n_az * n_el), np.complex64)
         return frames, out.astype(np.complex128).reshape(len(frames), self.S, n_az, n_el)
+
+    def synthetic_array_patterns_device(self, proc, velocities, calibrated: bool = False,
+                                        num_calibration_iters: int = 1) -> Tuple[np.ndarray, _lib.DeviceBuffer]:
+        """``(frames, buffer)``: the patterns of ``synthetic_array_patterns`` left in HBM, float32 ``[n_valid][n_az * n_el]``,
+        nothing downloaded."""
+        # every argument check comes before the first use of self.ctx / self.bufs
+        what = "synthetic_array_patterns"
+        if calibrated:
+            n_it = int(num_calibration_iters)
+            if not 1 <= n_it <= 8:
+                raise ValueError(f"{what}: num_calibration_iters {num_calibration_iters} is not in [1, 8]")
+            v, frames, P, dirs, n_az, n_el = self._synthetic_array_arguments(proc, velocities, what)
+        else:
+            valid, P = synthetic_array_geometry(proc, velocities)
+            frames = np.flatnonzero(valid)
+        P, d, lam = array_pattern_args(P, proc.d, proc.lambda_m, what)
+        n, E, T = P.shape[0], P.shape[2], d.shape[1] * d.shape[2]
+        if calibrated:
+            # the geometries are read where mmw_synth_array_calibrate left them; only rows the host route corrected are uploaded
+            key = (v, int(proc.stride), int(proc.num_frames), lam, n_it, n_az, n_el, frames, P, dirs)
+            have = self._synth_calib_key
+            if have is None or not all(np.array_equal(a, b) for a, b in zip(have, key)):
+                self.synthetic_array_calibrated_device(proc, velocities, n_it)
+            d_P = self.bufs.get("synth_calib_P", max(n, 1) * 3 * E * 8)
+            for q in self._synth_calib_stale:
+                d_P.upload(self.synth_geometry_calibrated[q], byte_offset=q * 3 * E * 8)
+            self._synth_calib_stale = []
+        else:
+            d_P = self.bufs.get("synth_pattern_P", max(n, 1) * 3 * E * 8)
+            if n:
+                d_P.upload(P)
+        self.d_synth_pattern = self.bufs.get("synth_pattern", max(n, 1) * T * 4)
+        array_patterns_on(self.ctx, d_P.ptr, n, E, d, lam, self.d_synth_pattern)
+        return frames.astype(np.int64), self.d_synth_pattern
+
+    def synthetic_array_patterns(self, proc, velocities, calibrated: bool = False,
+                                 num_calibration_iters: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """``(frames, patterns)``: the beam pattern float32 ``[n_valid, n_az, n_el]`` of every valid frame's synthetic array (the
+        reference's ``compute_synthetic_array_pattern``: ``|sum_e exp(j 2 pi d . p_e / lambda)|`` over the steering grid,
+        normalised per frame), one ``mmw_synth_array_pattern`` call on this pipeline's context.  ``calibrated=False``: the
+        geometries of ``synthetic_array_geometry`` -- ``batch.synthetic_array_patterns``; no cubes are read and ``velocities``
+        may have any number of rows.  ``calibrated=True``: the geometries ``synthetic_array_calibrated_device(proc, velocities,
+        num_calibration_iters)`` produced (``synth_geometry_calibrated``), read in place from its device buffer; the calibration
+        is run first unless its results for these arguments and the resident cubes are still there.  Scope as
+        ``synthetic_array``."""
+        frames, buf = self.synthetic_array_patterns_device(proc, velocities, calibrated, num_calibration_iters)
+        n_az, n_el = np.shape(proc.d)[1:]
+        out = buf.download((len(frames), n_az, n_el), np.float32) if len(frames) else np.zeros((0, n_az, n_el), np.float32)
+        return frames, out
 
     def _alloc_detect(self):
         F, V, cap = self.n_frames, self.V, self.cap

@@ -78,6 +78,66 @@ class SyntheticArrayBeamformerCore:
         self.beamformed_resp = out[0] if single else out
         return self.beamformed_resp
 
+    def compute_array_factor_at_angle(self, array_geometry: np.ndarray, steering_vector: np.ndarray) -> complex:
+        """The array factor of ``array_geometry [3, N]`` towards ``steering_vector [3]`` with unit signals at every element
+        (reference :615-640).  One direction: plain numpy on the host."""
+        return np.sum(np.exp(1j * 2 * np.pi * (np.asarray(steering_vector) @ np.asarray(array_geometry)) / self.lambda_m))
+
+    def compute_synthetic_array_pattern(self, array_geometry: np.ndarray) -> np.ndarray:
+        """The beam pattern float32 ``[n_az, n_el]`` of ``array_geometry [frames, 3, chirps]``: ``|array factor|`` over the
+        steering grid, normalised to its maximum (reference :642-670), one ``mmw_synth_array_pattern`` call."""
+        geom = np.asarray(array_geometry, dtype=np.float64)
+        if geom.ndim != 3 or geom.shape[1] != 3:
+            raise ValueError(f"compute_synthetic_array_pattern: array_geometry must be [frames, 3, chirps], got {geom.shape}")
+        P = geom.transpose((1, 0, 2)).reshape(1, 3, -1)
+        return array_patterns(P, self.d, self.lambda_m, ctx=self._ctx)[0]
+
+
+def array_pattern_args(P, d, lambda_m, what: str = "array_patterns"):
+    """The argument checks of ``array_patterns`` (no device is touched): ``(P float64 [n, 3, E], d float64 [3, n_az, n_el],
+    lambda_m)``."""
+    P = np.ascontiguousarray(P, dtype=np.float64)
+    if P.ndim != 3 or P.shape[1] != 3 or P.shape[2] < 1:
+        raise ValueError(f"{what}: P must be [n, 3, E] element positions with E >= 1, got {P.shape}")
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    if d.ndim != 3 or d.shape[0] != 3 or d.shape[1] < 1 or d.shape[2] < 1:
+        raise ValueError(f"{what}: d must be [3, n_az, n_el] steering directions, got {d.shape}")
+    lam = float(lambda_m)
+    if not (lam > 0 and np.isfinite(lam)):
+        raise ValueError(f"{what}: lambda_m {lambda_m} is not a positive finite wavelength")
+    if P.shape[0] * d.shape[1] * d.shape[2] >= 2**31 or P.shape[0] * 3 * P.shape[2] >= 2**31:
+        raise ValueError(f"{what}: P {P.shape} with {d.shape[1]} x {d.shape[2]} directions is beyond int32 entries: split the frames")
+    return P, d, lam
+
+
+def array_patterns_on(ctx: _lib.Context, d_P_ptr: int, n: int, E: int, d: np.ndarray, lam: float, d_pattern: _lib.DeviceBuffer,
+                      d_af: _lib.DeviceBuffer = None) -> None:
+    """``mmw_synth_array_pattern`` on a geometry table already in HBM (``d_P_ptr``: ``[n][3][E]`` float64)."""
+    dirs = np.ascontiguousarray(d.reshape(3, -1))
+    _lib.check(ctx.lib.mmw_synth_array_pattern(ctx.handle, d_P_ptr, n, E, dirs.ctypes.data_as(C.POINTER(C.c_double)), dirs.shape[1],
+                                               lam, d_pattern.ptr, d_af.ptr if d_af is not None else None))
+
+
+def array_patterns(P, d, lambda_m, ctx: _lib.Context = None, with_factor: bool = False):
+    """Beam patterns float32 ``[n, n_az, n_el]`` of the geometries ``P [n, 3, E]`` (element positions, the layout of
+    ``batch.synthetic_array_geometry``) over the directions ``d [3, n_az, n_el]``: per frame ``|sum_e exp(j 2 pi d . p_e /
+    lambda)|`` rounded to float32 and divided by its maximum -- the reference's ``compute_synthetic_array_pattern`` for every
+    frame in one ``mmw_synth_array_pattern`` call.  ``with_factor=True``: ``(patterns, factors)`` with the un-normalised
+    complex128 array factors ``[n, n_az, n_el]``."""
+    P, d, lam = array_pattern_args(P, d, lambda_m)
+    n, E, (n_az, n_el) = P.shape[0], P.shape[2], d.shape[1:]
+    if n == 0:
+        out = np.zeros((0, n_az, n_el), np.float32)
+        return (out, np.zeros((0, n_az, n_el), np.complex128)) if with_factor else out
+    ctx = ctx if ctx is not None else _lib.default_context()
+    T = n_az * n_el
+    d_P, d_pat = ctx.cached("array_patterns_P", P.nbytes), ctx.cached("array_patterns", n * T * 4)
+    d_af = ctx.cached("array_patterns_af", n * T * 16) if with_factor else None
+    d_P.upload(P)
+    array_patterns_on(ctx, d_P.ptr, n, E, d, lam, d_pat, d_af)
+    out = d_pat.download((n, n_az, n_el), np.float32)
+    return (out, d_af.download((n, n_az, n_el), np.complex128)) if with_factor else out
+
 
 # Bytes of snapshots per pass.  Measured (DESIGN.md 4.20, profiles/capon_range_angle.json): 1024 MiB is the fastest of 16 / 64 /
 # 256 / 1024 MiB and a single pass on both bench shapes; 256 MiB is within 1 % of it, the 64 MiB first guessed (a quarter of the

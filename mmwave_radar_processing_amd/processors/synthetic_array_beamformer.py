@@ -12,7 +12,10 @@ of a resident batch in one ``mmw_synth_array`` call, reading the windows in plac
 
 Calibration against targets of opportunity is ``SelfCalibratingSyntheticArrayProcessor`` (below; batched as
 ``FramePipeline.synthetic_array_calibrated`` on ``mmw_synth_array_calibrate``); the plain class keeps refusing
-``enable_calibration=True``.  Left out on purpose: the Cartesian ``griddata`` resampling of the image, which is presentation (and
+``enable_calibration=True``.  The beam pattern of a geometry -- the aperture the motion synthesised, with unit signals and no
+taper -- is ``compute_synthetic_array_pattern`` (one direction on the host: ``compute_array_factor_at_angle``); for every valid
+frame of a drive at once ``batch.synthetic_array_patterns`` / ``FramePipeline.synthetic_array_patterns`` on
+``mmw_synth_array_pattern``.  Left out on purpose: the Cartesian ``griddata`` resampling of the image, which is presentation (and
 raises upstream for more than one elevation bin).
 """
 from __future__ import annotations
@@ -108,6 +111,14 @@ class SyntheticArrayBeamformerProcessor(_Processor):
     def compute_synthetic_response(self, array_geometry: np.ndarray) -> np.ndarray:
         """complex128 ``[S, n_az, n_el]`` of the stored window with element positions ``array_geometry [num_frames, 3, Cv]``."""
         return self._core.compute_synthetic_response(self.history_acd_cube_valid_chirps, array_geometry)
+
+    def compute_array_factor_at_angle(self, array_geometry: np.ndarray, steering_vector: np.ndarray) -> complex:
+        """The array factor of ``array_geometry [3, N]`` towards ``steering_vector [3]``: unit signals, no taper (host numpy)."""
+        return self._core.compute_array_factor_at_angle(array_geometry, steering_vector)
+
+    def compute_synthetic_array_pattern(self, array_geometry: np.ndarray) -> np.ndarray:
+        """The beam pattern float32 ``[n_az, n_el]`` of ``array_geometry [num_frames, 3, Cv]``, normalised to its maximum."""
+        return self._core.compute_synthetic_array_pattern(array_geometry)
 
     def process(self, adc_cube: np.ndarray, current_vel, **kwargs) -> np.ndarray:
         """``adc_cube``: the RAW cube ``[num_rx, S, chirps_per_frame]``.  The image, or ``np.empty(0)`` while the gate is shut."""
