@@ -17,11 +17,10 @@
 #include <cmath>
 
 #include "../../include/mmwgpu.h"
+#include "mmw_dopaz_codes.h"             // DZP_NONE, DZP_UNDECIDED
 
 namespace mmw {
 
-constexpr int DZP_NONE = -1;            // the line has no (qualifying) peak
-constexpr int DZP_UNDECIDED = -2;       // a comparison fell inside the band, or the frame holds a non-finite value
 constexpr int DZP_LS = 65;              // doubles per row of the LDS image: an odd stride, so that the 64 threads of a wave, each
                                         // walking a row of its own, read 32 distinct banks per half wave (ds_read_b64)
 constexpr int DZP_LDS_HEAD = 64;        // bytes in front of the image: four wave maxima, four non-finite flags

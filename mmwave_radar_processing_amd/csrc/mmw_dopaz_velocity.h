@@ -14,6 +14,8 @@
 // column: a fit is sum(h y) / sum(h h) here and an SVD solve there.  A decision that this difference could turn is not taken:
 // the pair is FLAGGED (MMW_DOPAZ_FLAG_*), its row zeroed, and the caller lets scikit-learn decide.  The bands are derived in
 // DESIGN.md 4.23.  Nothing random and nothing transcendental runs here: subsets, trial caps, cos, sin and the angles are tables.
+// The trial loop, the bands and the wavefront reduction are mmw_lsq_core.h's, shared with the other estimators; this header holds
+// the two waves, the one-column model, the peak list, the refit and the flags.
 // This unit is compiled with -ffp-contract=off: every product and difference below is one round-to-nearest operation.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,14 +25,14 @@
 #include <cstdint>
 
 #include "../../include/mmwgpu.h"
+#include "mmw_dopaz_codes.h"              // DZP_UNDECIDED
+#include "mmw_lsq_core.h"
 
 namespace mmw {
 
 constexpr int DZV_TRIALS = 20;            // max_trials
 constexpr int DZV_MIN_SAMPLES = 10;       // min_samples
 constexpr int DZV_LANES = 64;
-constexpr double DZV_U = 1.1102230246251565e-16;   // 2^-53
-constexpr int DZV_PEAK_UNDECIDED = -2;    // mmw_dopaz_peaks.h: DZP_UNDECIDED
 
 // offset of the trial caps of N points in the table: rows of N + 1 entries for N = 10, 11, ...
 __host__ __device__ inline long dzv_trials_off(int N) {
@@ -52,16 +54,10 @@ struct DzvArgs {
     int32_t *flags;              // [G][F]
 };
 
-struct DzvSum {
-    __host__ __device__ static double op(double a, double b) { return a + b; }
-};
-struct DzvMax {
-    __host__ __device__ static double op(double a, double b) { return a > b ? a : b; }
-};
-
 // The 64 lanes as a loop: fn(lane, acc) fills the lane's partials, the halving tree joins them in the order of the device's
 // shuffle tree (lane l takes lane l + off for off = 32, 16, ... 1; lane 0 holds the total).
 struct DzvWaveHost {
+    static constexpr int width = DZV_LANES;
     template <int K, class Op, class Fn> void reduce(double (&tot)[K], Fn fn) const {
         double v[DZV_LANES][K];
         for (int l = 0; l < DZV_LANES; ++l) {
@@ -86,61 +82,59 @@ struct DzvWaveHost {
 
 #if defined(__HIPCC__)
 struct DzvWaveDevice {
+    static constexpr int width = DZV_LANES;
     int lane;
     template <int K, class Op, class Fn> __device__ void reduce(double (&tot)[K], Fn fn) const {
         fn(lane, tot);
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            double v = tot[k];
-            for (int off = DZV_LANES / 2; off > 0; off >>= 1) v = Op::op(v, __shfl_down(v, off));
-            tot[k] = __shfl(v, 0);
-        }
+        lsq_wave_reduce<K, Op>(tot);
     }
     template <class Keep, class Emit> __device__ int compact(int n, Keep keep, Emit emit) const {
         int cnt = 0;
         for (int base = 0; base < n; base += DZV_LANES) {
             const int r = base + lane;
             const bool k = r < n && keep(r);
-            const unsigned long long mask = __ballot(k);
-            if (k) emit(r, cnt + __popcll(mask & ((1ull << lane) - 1ull)));
-            cnt += __popcll(mask);
+            int kept;
+            const int slot = lsq_wave_slot(k, lane, &kept);
+            if (k) emit(r, cnt + slot);
+            cnt += kept;
         }
         return cnt;
     }
     // the list's LDS stores of all lanes are complete and visible before any lane's loads behind this point
-    __device__ void sync() const {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
+    __device__ void sync() const { lsq_wave_sync(); }
     template <class Fn> __device__ void lane0(Fn fn) const {
         if (lane == 0) fn();
     }
 };
 #endif
 
-// band on a single-column fit's coefficient against an SVD solve of the same n points: |c| and |y| / |h| in 2-norms
-__host__ __device__ inline double dzv_band_coef(int n, double c, double syy, double shh) {
-    return 8.0 * (n + 8) * DZV_U * (fabs(c) + (shh > 0.0 ? sqrt(syy / shh) : 0.0));
-}
+// The model of lsq_ransac_trials with one column h: c = sum(h y) / sum(h h) against an SVD solve of the same points
+struct DzvModel {
+    const double *hc, *ys;
+    double ymax, hmax, c, band_c, band_r;
+    struct Sums {
+        double hy, hh, yy;
+    };
+    __host__ __device__ void add(Sums &s, int i) const {
+        const double h = hc[i], y = ys[i];
+        s.hy += h * y;
+        s.hh += h * h;
+        s.yy += y * y;
+    }
+    // c is 0 for h == 0 (the minimum-norm solution of the SVD solve); its band takes |c| and |y| / |h| in 2-norms (the condition
+    // number of one column is 1); not trusted: a sum(h h) too small or too large
+    __host__ __device__ bool solve(const Sums &s, int n) {
+        c = s.hh == 0.0 ? 0.0 : s.hy / s.hh;
+        band_c = lsq_band_coef(n, 1.0, fabs(c) + (s.hh > 0.0 ? sqrt(s.yy / s.hh) : 0.0));
+        band_r = lsq_band_residual(band_c, hmax, ymax, fabs(c));
+        return s.hh == 0.0 || (s.hh >= 1e-200 && s.hh <= 1e200);
+    }
+    __host__ __device__ double residual(int i) const { return fabs(ys[i] - hc[i] * c); }
+};
 
-// R^2 = 1 - a / b with r2_score's conventions (a == 0: 1; b == 0: 0) and its band from the bands of a and b;
-// *loose: the denominator is not clearly non-zero
-__host__ __device__ inline double dzv_r2(double a, double b, double da, double db, double *band, bool *loose) {
-    *loose = !(b > 4.0 * db);
-    *band = 0.0;
-    if (a == 0.0) return 1.0;
-    if (b == 0.0) return 0.0;
-    *band = 2.0 * (da + (a / b) * db) / b;
-    return 1.0 - a / b;
-}
-
-// c = sum(h y) / sum(h h), or 0 for h == 0 (the minimum-norm solution of the SVD solve); *bad: a sum too small or too large
-// to be trusted
-__host__ __device__ inline double dzv_coef(double shy, double shh, bool *bad) {
-    if (shh == 0.0) return 0.0;
-    if (!(shh >= 1e-200 && shh <= 1e200)) *bad = true;
-    return shy / shh;
+__host__ __device__ inline int dzv_stop_flag(LsqStop stop) {
+    return stop == LSQ_STOP_RESIDUAL ? MMW_DOPAZ_FLAG_RESIDUAL : stop == LSQ_STOP_SCORE_TIE ? MMW_DOPAZ_FLAG_SCORE_TIE
+         : stop == LSQ_STOP_FIT ? MMW_DOPAZ_FLAG_NONFINITE : stop == LSQ_STOP_TABLE ? MMW_DOPAZ_FLAG_TABLES : 0;
 }
 
 // One (group, frame).  hc / yc: room for n_rows doubles each, the wave's own.  Every branch below is taken by the whole wave.
@@ -157,7 +151,7 @@ __host__ __device__ inline void dzv_pair(const Wave &w, const DzvArgs &a, int g,
     {
         const int za = a.zero[(long)a.g_az * a.F + f];
         const int ze = a.g_el >= 0 ? a.zero[(long)a.g_el * a.F + f] : -1;
-        if (za == DZV_PEAK_UNDECIDED || ze == DZV_PEAK_UNDECIDED) flags |= MMW_DOPAZ_FLAG_UNDECIDED;
+        if (za == DZP_UNDECIDED || ze == DZP_UNDECIDED) flags |= MMW_DOPAZ_FLAG_UNDECIDED;
         else if (za < -1 || ze < -1 || za >= m || ze >= m) flags |= MMW_DOPAZ_FLAG_TABLES;
         else if (za >= 0 && ze >= 0) vx = (-1.0 * (vel[za] + vel[ze])) / 2.0;
         else if (za >= 0) vx = -1.0 * vel[za];
@@ -187,9 +181,9 @@ __host__ __device__ inline void dzv_pair(const Wave &w, const DzvArgs &a, int g,
             });
         w.sync();
         double st[4] = {0.0, 0.0, 0.0, 0.0};          // max |y|, max |h|, non-finite entries, entries that are no index
-        w.template reduce<4, DzvMax>(st, [&](int lane, double *acc) {
+        w.template reduce<4, LsqMax>(st, [&](int lane, double *acc) {
             for (int r = lane; r < m; r += DZV_LANES) {
-                if (rp[r] == DZV_PEAK_UNDECIDED) acc[3] = 2.0;
+                if (rp[r] == DZP_UNDECIDED) acc[3] = 2.0;
                 else if (rp[r] < -1 || rp[r] >= n_cols) acc[3] = acc[3] > 1.0 ? acc[3] : 1.0;
             }
             for (int j = lane; j < N; j += DZV_LANES) {
@@ -212,101 +206,17 @@ __host__ __device__ inline void dzv_pair(const Wave &w, const DzvArgs &a, int g,
         else if (flags == 0) {
             const int32_t *sub = a.subsets + (long)(N - DZV_MIN_SAMPLES) * DZV_TRIALS * DZV_MIN_SAMPLES;
             const int32_t *tab = a.trials + dzv_trials_off(N);
-            int max_trials = DZV_TRIALS, n_trials = 0, n_best = 1;
-            double score_best = -HUGE_VAL, band_best = 0.0, cb = 0.0;
-            bool found = false;
-            while (flags == 0 && n_trials < max_trials) {
-                const int t = n_trials++;
-                // the subset's fit: every lane computes the same ten-point sums
-                double shy = 0.0, shh = 0.0, syy = 0.0;
-                for (int k = 0; k < DZV_MIN_SAMPLES; ++k) {
-                    const int i = sub[t * DZV_MIN_SAMPLES + k];
-                    if ((unsigned)i >= (unsigned)N) {
-                        flags |= MMW_DOPAZ_FLAG_TABLES;
-                        break;
-                    }
-                    const double h = hc[i], y = yc[i];
-                    shy += h * y;
-                    shh += h * h;
-                    syy += y * y;
-                }
-                if (flags) break;
-                bool bad = false;
-                const double c = dzv_coef(shy, shh, &bad);
-                if (bad) {
-                    flags |= MMW_DOPAZ_FLAG_NONFINITE;
-                    break;
-                }
-                const double band_c = dzv_band_coef(DZV_MIN_SAMPLES, c, syy, shh);
-                const double band_r = hmax * band_c + 8.0 * DZV_U * (ymax + hmax * fabs(c));
-                // residuals of all points: inlier count, sum of y, of r^2 and of |r| over the inliers, residuals inside the band
-                double s1[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-                w.template reduce<5, DzvSum>(s1, [&](int lane, double *acc) {
-                    for (int j = lane; j < N; j += DZV_LANES) {
-                        const double r = fabs(yc[j] - hc[j] * c);
-                        if (fabs(r - thr) <= band_r) acc[4] += 1.0;
-                        if (r <= thr) {
-                            acc[0] += 1.0;
-                            acc[1] += yc[j];
-                            acc[2] += r * r;
-                            acc[3] += r;
-                        }
-                    }
-                });
-                if (s1[4] != 0.0) {
-                    flags |= MMW_DOPAZ_FLAG_RESIDUAL;
-                    break;
-                }
-                const int mi = (int)s1[0];
-                if (mi < n_best) continue;               // fewer inliers: skipped before it is scored
-                double score = NAN, band_s = 0.0;
-                if (mi >= 2) {                           // r2_score of fewer than two samples is nan
-                    const double ybar = s1[1] / mi;
-                    double s2[1] = {0.0};
-                    w.template reduce<1, DzvSum>(s2, [&](int lane, double *acc) {
-                        for (int j = lane; j < N; j += DZV_LANES)
-                            if (fabs(yc[j] - hc[j] * c) <= thr) {
-                                const double dv = yc[j] - ybar;
-                                acc[0] += dv * dv;
-                            }
-                    });
-                    const double e = 2.0 * (mi + 4) * DZV_U * ymax;
-                    const double da = 2.0 * band_r * s1[3] + mi * band_r * band_r + (mi + 4) * DZV_U * s1[2];
-                    const double db = 2.0 * e * sqrt(mi * s2[0]) + mi * e * e + (mi + 4) * DZV_U * s2[0];
-                    bool loose;
-                    score = dzv_r2(s1[2], s2[0], da, db, &band_s, &loose);
-                    if (loose) band_s = HUGE_VAL;
-                }
-                if (mi == n_best && found && fabs(score - score_best) <= band_s + band_best) {
-                    // tied within rounding: immaterial when both trials select the same inliers (the refit sees the same points)
-                    double df[1] = {0.0};
-                    w.template reduce<1, DzvSum>(df, [&](int lane, double *acc) {
-                        for (int j = lane; j < N; j += DZV_LANES)
-                            if ((fabs(yc[j] - hc[j] * c) <= thr) != (fabs(yc[j] - hc[j] * cb) <= thr)) acc[0] += 1.0;
-                    });
-                    if (df[0] != 0.0) {
-                        flags |= MMW_DOPAZ_FLAG_SCORE_TIE;
-                        break;
-                    }
-                    continue;
-                }
-                if (mi == n_best && score < score_best) continue;
-                n_best = mi;
-                score_best = score;
-                band_best = band_s;
-                cb = c;
-                found = true;
-                const int dyn = tab[mi];
-                max_trials = dyn < max_trials ? dyn : max_trials;
-            }
+            DzvModel best{hc, yc, ymax, hmax, 0.0, 0.0, 0.0};
+            bool found;
+            flags |= dzv_stop_flag(lsq_ransac_trials(w, N, thr, ymax, sub, DZV_MIN_SAMPLES, DZV_TRIALS, tab, &best, &found));
 
             if (flags == 0 && !found) status = MMW_DOPAZ_STATUS_FAILED;      // no accepted trial: the class's ValueError path
             if (flags == 0 && found) {
                 // refit on the best trial's inliers (the same residual arithmetic gives the same mask)
                 double s3[5] = {0.0, 0.0, 0.0, 0.0, 0.0};                      // sum hy, hh, yy, count, sum y
-                w.template reduce<5, DzvSum>(s3, [&](int lane, double *acc) {
+                w.template reduce<5, LsqSum>(s3, [&](int lane, double *acc) {
                     for (int j = lane; j < N; j += DZV_LANES)
-                        if (fabs(yc[j] - hc[j] * cb) <= thr) {
+                        if (best.residual(j) <= thr) {
                             const double h = hc[j], y = yc[j];
                             acc[0] += h * y;
                             acc[1] += h * h;
@@ -317,39 +227,34 @@ __host__ __device__ inline void dzv_pair(const Wave &w, const DzvArgs &a, int g,
                 });
                 const int mi = (int)s3[3];
                 inliers = mi;
-                bool bad = false;
-                const double c = dzv_coef(s3[0], s3[1], &bad);
-                if (bad) flags |= MMW_DOPAZ_FLAG_NONFINITE;
-                const double band_c = dzv_band_coef(mi, c, s3[2], s3[1]);
+                DzvModel fit = best;
+                if (!fit.solve(DzvModel::Sums{s3[0], s3[1], s3[2]}, mi)) flags |= MMW_DOPAZ_FLAG_NONFINITE;
+                const double c = fit.c;
                 const double share = (double)mi / (double)N;
-                if (fabs(share - a.share_thr) <= 4.0 * DZV_U) flags |= MMW_DOPAZ_FLAG_SHARE;
+                if (fabs(share - a.share_thr) <= 4.0 * LSQ_U) flags |= MMW_DOPAZ_FLAG_SHARE;
                 double r2 = 0.0;
                 if (!standard && mi < 2) flags |= MMW_DOPAZ_FLAG_R2;             // model.score of one sample: nan
                 else if (!standard || mi > 3) {
-                    const double band_r = hmax * band_c + 8.0 * DZV_U * (ymax + hmax * fabs(c));
                     const double ybar = s3[4] / mi;
                     double s4[3] = {0.0, 0.0, 0.0};                             // sum r^2, sum |r|, sum (y - ybar)^2 over the inliers
-                    w.template reduce<3, DzvSum>(s4, [&](int lane, double *acc) {
+                    w.template reduce<3, LsqSum>(s4, [&](int lane, double *acc) {
                         for (int j = lane; j < N; j += DZV_LANES)
-                            if (fabs(yc[j] - hc[j] * cb) <= thr) {
-                                const double r = fabs(yc[j] - hc[j] * c);
+                            if (best.residual(j) <= thr) {
+                                const double r = fit.residual(j);
                                 const double dv = yc[j] - ybar;
                                 acc[0] += r * r;
                                 acc[1] += r;
                                 acc[2] += dv * dv;
                             }
                     });
-                    const double e = 2.0 * (mi + 4) * DZV_U * ymax;
-                    const double da = 2.0 * band_r * s4[1] + mi * band_r * band_r + (mi + 4) * DZV_U * s4[0];
-                    const double db = 2.0 * e * sqrt(mi * s4[2]) + mi * e * e + (mi + 4) * DZV_U * s4[2];
                     double band;
                     bool loose;
-                    r2 = dzv_r2(s4[0], s4[2], da, db, &band, &loose);
+                    r2 = lsq_r2_of_sums(mi, ymax, fit.band_r, s4[0], s4[1], s4[2], &band, &loose);
                     if ((loose && ymax != 0.0) || fabs(r2 - a.r2_thr) <= band) flags |= MMW_DOPAZ_FLAG_R2;
                 }
                 double vy = c;
                 if (!standard) {
-                    if (ymax != 0.0 && fabs(c) <= band_c) flags |= MMW_DOPAZ_FLAG_A_ZERO;   // y == 0 throughout: a is 0 there as here
+                    if (ymax != 0.0 && fabs(c) <= fit.band_c) flags |= MMW_DOPAZ_FLAG_A_ZERO;   // y == 0 throughout: a is 0 there as here
                     vy = c != 0.0 ? -1.0 / c : 0.0;
                 }
                 res[1] = vy;

@@ -13,7 +13,9 @@
 // The class fits by inv(H^T H) (LAPACK), the kernel by the adjugate of the same dim x dim Gram matrix, and the two sum in
 // different orders.  A decision that this difference could turn is not taken: the frame is FLAGGED (MMW_VEHICLE_FLAG_*), its row
 // zeroed, and the caller lets the host class decide.  The bands are derived in DESIGN.md 4.25.  Nothing random and nothing
-// transcendental runs here: the draws are a host-made table.  This unit is compiled with -ffp-contract=off.
+// transcendental runs here: the draws are a host-made table.  The solve, the bands, the reductions and the unit-row loader are
+// mmw_lsq_core.h's, shared with the other estimators; the iteration loop is the class's own and lives here.
+// This unit is compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,11 +23,10 @@
 #include <cstdint>
 
 #include "../../include/mmwgpu.h"
+#include "mmw_lsq_core.h"
 
 namespace mmw {
 
-constexpr double VV_COND_CAP = 1e6;                 // largest accepted bound tr(G)^dim / det(G) >= cond(G) of a Gram matrix
-constexpr double VV_U = 1.1102230246251565e-16;     // 2^-53
 constexpr int VV_GRID_MAX = 2048;                   // workgroups of a batch launch; more frames are walked in further passes
 constexpr int VV_WAVES_BATCH = 4, VV_WAVES_CHAIN = 16;
 constexpr int VV_REC = 9;                           // doubles an iteration leaves: error, band, subset fit [3], refit [3], its band
@@ -49,77 +50,6 @@ inline size_t vehicle_lds_bytes(int cap, int max_iters) {
 }
 
 #if defined(__HIPCC__)
-struct VvSum {
-    __device__ static double op(double a, double b) { return a + b; }
-};
-struct VvMax {
-    __device__ static double op(double a, double b) { return a > b ? a : b; }
-};
-
-// every lane of the wavefront gets the K totals: lane partials joined by the halving tree, lane 0's result broadcast
-template <int K> __device__ __forceinline__ void vv_wave_sum(double (&v)[K]) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double t = v[k];
-        for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off);
-        v[k] = __shfl(t, 0);
-    }
-}
-
-// every thread of the NW wavefronts gets the K totals (lanes by the halving tree, then the wavefronts in order); red: [NW][K]
-template <int K, typename Op, int NW> __device__ __forceinline__ void vv_block_reduce(double (&v)[K], double *red) {
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-        for (int off = 32; off > 0; off >>= 1) v[k] = Op::op(v[k], __shfl_down(v[k], off));
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();                                             // the previous totals have been read
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < K; ++k) red[wave * K + k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double t = red[k];
-        for (int w = 1; w < NW; ++w) t = Op::op(t, red[w * K + k]);
-        v[k] = t;
-    }
-}
-
-// G c = b for the symmetric dim x dim G (g: xx, xy, yy, xz, yz, zz) by the adjugate; cond: tr(G)^dim / det(G) >= cond_2(G) for a
-// positive definite G, +inf when det <= 0.
-__device__ __forceinline__ void vv_solve(int dim, const double *g, const double *b, double *c, double *cond) {
-    double det, tr;
-    if (dim == 2) {
-        det = g[0] * g[2] - g[1] * g[1];
-        tr = g[0] + g[2];
-        c[0] = (g[2] * b[0] - g[1] * b[1]) / det;
-        c[1] = (g[0] * b[1] - g[1] * b[0]) / det;
-        c[2] = 0.0;
-        *cond = tr * tr / det;
-    } else {
-        const double a00 = g[2] * g[5] - g[4] * g[4], a01 = g[3] * g[4] - g[1] * g[5], a02 = g[1] * g[4] - g[3] * g[2];
-        const double a11 = g[0] * g[5] - g[3] * g[3], a12 = g[1] * g[3] - g[0] * g[4], a22 = g[0] * g[2] - g[1] * g[1];
-        det = g[0] * a00 + g[1] * a01 + g[3] * a02;
-        tr = g[0] + g[2] + g[5];
-        c[0] = (a00 * b[0] + a01 * b[1] + a02 * b[2]) / det;
-        c[1] = (a01 * b[0] + a11 * b[1] + a12 * b[2]) / det;
-        c[2] = (a02 * b[0] + a12 * b[1] + a22 * b[2]) / det;
-        *cond = tr * tr * tr / det;
-    }
-    if (!(det > 0.0) || !(*cond == *cond)) *cond = __builtin_huge_val();
-}
-
-__device__ __forceinline__ double vv_abs1(const double *c) { return fabs(c[0]) + fabs(c[1]) + fabs(c[2]); }
-
-// band on the coefficients of a fit over n unit rows against the class's inv(H^T H) solve of the same points
-__device__ __forceinline__ double vv_band_coef(int n, double cond, double scale) {
-    return 8.0 * ((double)n + 8.0) * VV_U * cond * scale;
-}
-
-// band on a squared residual r * r whose residual is known to band_r
-__device__ __forceinline__ double vv_band_sq(double r, double band_r) {
-    return 2.0 * fabs(r) * band_r + band_r * band_r + 4.0 * VV_U * r * r;
-}
-
 __device__ __forceinline__ bool vv_drawn(const int32_t *dr, int ppf, int j) {
     bool in = false;
     for (int k = 0; k < ppf; ++k) in |= dr[k] == j;
@@ -133,7 +63,7 @@ struct VvFrame {
     // point j belongs to the refit of an iteration: drawn, or within the threshold of the drawn points' fit c
     __device__ __forceinline__ bool member(const int32_t *dr, const double *c, int j) const {
         if (vv_drawn(dr, ppf, j)) return true;
-        const double r = ys[j] - ((hx[j] * c[0] + hy[j] * c[1]) + hz[j] * c[2]);
+        const double r = lsq_residual(hx[j], hy[j], hz[j], ys[j], c);
         return r * r < thr;
     }
 };
@@ -182,35 +112,20 @@ template <int NW> __global__ __launch_bounds__(NW * 64) void k_vehicle_ransac(Vv
                 if (ini[k] != ini[k]) has_init = false;
             }
         }
-        if (has_init && !(vv_abs1(ini) <= DBL_MAX)) flags |= MMW_VEHICLE_FLAG_NONFINITE;
+        if (has_init && !(lsq_abs1(ini) <= DBL_MAX)) flags |= MMW_VEHICLE_FLAG_NONFINITE;
 
-        // H = p / |p| (the norm: sqrt of the left-to-right sum of squares, as np.linalg.norm(axis=1)), y = v
-        double st[2] = {0.0, 0.0};                                // max |y|, non-finite entries
+        double ymax;                                              // H = p / |p|, y = v
         const double4 *p = reinterpret_cast<const double4 *>(a.points) + f * (long)cap;
-        for (int i = tid; i < N0; i += NW * 64) {
-            const double4 q = p[i];
-            double ss = q.x * q.x + q.y * q.y;
-            if (dim == 3) ss = ss + q.z * q.z;
-            const double nrm = __dsqrt_rn(ss);
-            const double x = q.x / nrm, y = q.y / nrm, z = dim == 3 ? q.z / nrm : 0.0;
-            hx[i] = x;
-            hy[i] = y;
-            hz[i] = z;
-            ys[i] = q.w;
-            const double s = fabs(x) + fabs(y) + fabs(z) + fabs(q.w);
-            if (!(s <= DBL_MAX)) st[1] = 1.0;
-            else if (fabs(q.w) > st[0]) st[0] = fabs(q.w);
-        }
-        vv_block_reduce<2, VvMax, NW>(st, red);
-        const double ymax = st[0];
-        if (st[1] != 0.0) flags |= MMW_VEHICLE_FLAG_NONFINITE;
+        if (lsq_load_unit_rows<NW, LSQ_JOIN_IN_ORDER>(p, N0, dim, false, hx, hy, hz, ys, red, &ymax))
+            flags |= MMW_VEHICLE_FLAG_NONFINITE;
 
         // the static filter: points whose speed the initial estimate explains, kept in order (one wavefront compacts in place);
         // a frame below num_close_pts points is empty before the filter is asked
         int N = N0;
         if (has_init && flags == 0 && N0 >= a.ncp) {
             if (wave == 0) {
-                const double band_r = 8.0 * VV_U * (ymax + vv_abs1(ini)) + ini_band;
+                const double band_r = lsq_band_residual(ini_band, 1.0, ymax, lsq_abs1(ini));
+                const double neg_ini[3] = {-ini[0], -ini[1], -ini[2]};   // the estimate is the vehicle's velocity, the fit its negative
                 int cnt = 0;
                 bool near = false;
                 for (int base = 0; base < N0; base += 64) {
@@ -219,26 +134,18 @@ template <int NW> __global__ __launch_bounds__(NW * 64) void k_vehicle_ransac(Vv
                     bool keep = false, nr = false;
                     if (j < N0) {
                         x = hx[j], y = hy[j], z = hz[j], v = ys[j];
-                        const double r = v - ((x * -ini[0] + y * -ini[1]) + z * -ini[2]);
+                        const double r = lsq_residual(x, y, z, v, neg_ini);
                         const double e = r * r;
-                        nr = fabs(e - a.static_thr) <= vv_band_sq(r, band_r);
+                        nr = fabs(e - a.static_thr) <= lsq_band_sq(r, band_r);
                         keep = e < a.static_thr;
                     }
-                    const unsigned long long kept = __ballot(keep);
-                    const unsigned long long close = __ballot(nr);
-                    near = near || close != 0ull;
-                    // every lane holds its point in registers before any lane stores (a store's slot is at or below its own)
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    if (keep) {
-                        const int pos = cnt + __popcll(kept & ((1ull << lane) - 1ull));
-                        hx[pos] = x, hy[pos] = y, hz[pos] = z, ys[pos] = v;
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    cnt += __popcll(kept);
+                    int kept;
+                    const int pos = cnt + lsq_wave_slot(keep, lane, &kept);
+                    near = near || __ballot(nr) != 0ull;
+                    lsq_wave_sync();       // every lane holds its point in registers before any lane stores (at or below its own slot)
+                    if (keep) hx[pos] = x, hy[pos] = y, hz[pos] = z, ys[pos] = v;
+                    lsq_wave_sync();
+                    cnt += kept;
                 }
                 if (lane == 0) {
                     misc[4] = (double)cnt;
@@ -270,37 +177,31 @@ template <int NW> __global__ __launch_bounds__(NW * 64) void k_vehicle_ransac(Vv
                 }
                 // the drawn points' fit: every lane computes the same sums
                 double g[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0}, c[3], cond;
-                for (int k = 0; k < ppf; ++k) {
-                    const int i = dr[k];
-                    const double x = hx[i], y = hy[i], z = hz[i], v = ys[i];
-                    g[0] += x * x, g[1] += x * y, g[2] += y * y, g[3] += x * z, g[4] += y * z, g[5] += z * z;
-                    b[0] += x * v, b[1] += y * v, b[2] += z * v;
-                }
-                vv_solve(dim, g, b, c, &cond);
-                if (!(cond <= VV_COND_CAP)) {
+                for (int k = 0; k < ppf; ++k) lsq_gram_add(g, b, hx[dr[k]], hy[dr[k]], hz[dr[k]], ys[dr[k]]);
+                lsq_gram_solve(dim, g, b, c, &cond);
+                if (!(cond <= LSQ_COND_CAP)) {
                     wf |= MMW_VEHICLE_FLAG_COND;
                     break;
                 }
-                const double scale = ymax + vv_abs1(c);
-                const double band_r = vv_band_coef(ppf, cond, scale) + 8.0 * VV_U * scale;
+                const double c1 = lsq_abs1(c);
+                const double band_r = lsq_band_residual(lsq_band_coef(ppf, cond, ymax + c1), 1.0, ymax, c1);
                 // the refit's members: count, residuals inside the band of the threshold, their Gram sums
                 double s[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
                 for (int j = lane; j < N; j += 64) {
                     const double x = hx[j], y = hy[j], z = hz[j], v = ys[j];
                     bool in = vv_drawn(dr, ppf, j);
                     if (!in) {
-                        const double r = v - ((x * c[0] + y * c[1]) + z * c[2]);
+                        const double r = lsq_residual(x, y, z, v, c);
                         const double e = r * r;
-                        if (fabs(e - a.fit_thr) <= vv_band_sq(r, band_r)) s[1] += 1.0;
+                        if (fabs(e - a.fit_thr) <= lsq_band_sq(r, band_r)) s[1] += 1.0;
                         in = e < a.fit_thr;
                     }
                     if (in) {
                         s[0] += 1.0;
-                        s[2] += x * x, s[3] += x * y, s[4] += y * y, s[5] += x * z, s[6] += y * z, s[7] += z * z;
-                        s[8] += x * v, s[9] += y * v, s[10] += z * v;
+                        lsq_gram_add(s + 2, s + 8, x, y, z, v);
                     }
                 }
-                vv_wave_sum<11>(s);
+                lsq_wave_reduce<11, LsqSum>(s);
                 if (s[1] != 0.0) {
                     wf |= MMW_VEHICLE_FLAG_RESIDUAL;
                     break;
@@ -309,24 +210,24 @@ template <int NW> __global__ __launch_bounds__(NW * 64) void k_vehicle_ransac(Vv
                 double mse = __builtin_huge_val(), band = 0.0, band_c2 = 0.0, c2[3] = {0.0, 0.0, 0.0};
                 if (m > a.ncp) {                                    // consensus: refit on every member, their mean squared error
                     double cond2;
-                    vv_solve(dim, s + 2, s + 8, c2, &cond2);
-                    if (!(cond2 <= VV_COND_CAP)) {
+                    lsq_gram_solve(dim, s + 2, s + 8, c2, &cond2);
+                    if (!(cond2 <= LSQ_COND_CAP)) {
                         wf |= MMW_VEHICLE_FLAG_COND;
                         break;
                     }
-                    const double scale2 = ymax + vv_abs1(c2);
-                    band_c2 = vv_band_coef(m, cond2, scale2);
-                    const double band_r2 = band_c2 + 8.0 * VV_U * scale2;
+                    const double c21 = lsq_abs1(c2);
+                    band_c2 = lsq_band_coef(m, cond2, ymax + c21);
+                    const double band_r2 = lsq_band_residual(band_c2, 1.0, ymax, c21);
                     double q[2] = {0.0, 0.0};                       // sum r^2, sum |r|
                     for (int j = lane; j < N; j += 64)
                         if (fr.member(dr, c, j)) {
-                            const double r = ys[j] - ((hx[j] * c2[0] + hy[j] * c2[1]) + hz[j] * c2[2]);
+                            const double r = lsq_residual(hx[j], hy[j], hz[j], ys[j], c2);
                             q[0] += r * r;
                             q[1] += fabs(r);
                         }
-                    vv_wave_sum<2>(q);
+                    lsq_wave_reduce<2, LsqSum>(q);
                     mse = q[0] / m;
-                    band = (2.0 * band_r2 * q[1] + m * band_r2 * band_r2 + (m + 4) * VV_U * q[0]) / m + 2.0 * VV_U * mse;
+                    band = lsq_band_sum_sq(m, band_r2, q[1], q[0]) / m + 2.0 * LSQ_U * mse;
                 }
                 if (lane == 0) {
                     double *rc = rec + (size_t)it * VV_REC;
@@ -360,7 +261,7 @@ template <int NW> __global__ __launch_bounds__(NW * 64) void k_vehicle_ransac(Vv
                     double df[1] = {0.0};
                     for (int j = tid; j < N; j += NW * 64)
                         if (fr.member(tab + (long)it * ppf, rc + 2, j) != fr.member(tab + (long)best * ppf, rb + 2, j)) df[0] += 1.0;
-                    vv_block_reduce<1, VvSum, NW>(df, red);
+                    lsq_block_reduce<1, LsqSum, NW, LSQ_JOIN_IN_ORDER>(df, red);
                     if (df[0] != 0.0) flags |= MMW_VEHICLE_FLAG_ERROR_TIE;
                 }
             }
