@@ -106,8 +106,9 @@ def test_point_clouds_device_on_the_non_power_of_two_golden_frame(golden):
         assert a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
-def run_kernel(c, points, dim, r2_thr=0.6, cap=None):
-    """The frames ``points`` through mmw_ego_velocity_ransac with the recorded tables: (out [F, dim + 2], flags, masks)."""
+def run_kernel(c, points, dim, r2_thr=0.6, cap=None, tables=None):
+    """The frames ``points`` through mmw_ego_velocity_ransac with the recorded tables, or with ``tables(subsets, row, tab, offs)``'s
+    edition of them: (out [F, dim + 2], flags, masks)."""
     ctx = _lib.default_context()
     cap = cap or c.cap
     F = len(points)
@@ -115,7 +116,7 @@ def run_kernel(c, points, dim, r2_thr=0.6, cap=None):
     packed = np.zeros((F, cap, 4))
     for f, p in enumerate(points):
         packed[f, :len(p)] = p
-    subsets, row, tab, offs = c.tables_for(counts)
+    subsets, row, tab, offs = c.tables_for(counts) if tables is None else tables(*c.tables_for(counts))
     bufs = []
 
     def dev(arr):

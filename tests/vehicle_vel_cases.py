@@ -17,33 +17,69 @@ def unit_rows(points, dim):
     return p / np.sqrt((p * p).sum(axis=1))[:, None]
 
 
-def _cond_bound(G):
-    """tr(G)^dim / det(G) >= cond_2(G): the bound the kernel's bands are computed from."""
+def cond_bound(G):
+    """tr(G)^dim / det(G) >= cond_2(G): the bound the kernels' bands are computed from."""
     det = np.linalg.det(G)
     return np.trace(G) ** len(G) / det if det > 0 else np.inf
 
 
-def _band_sq(r, band_r):
+def band_coef(n, cond, scale):
+    """band_c of a fit over n points: scale = y_max + |c|_1."""
+    return 8.0 * (n + 8) * U * cond * scale
+
+
+def band_residual(band_c, ymax, c1):
+    """band_r of a residual on a unit row from the band of its coefficients (0: an estimate that was not fitted)."""
+    return band_c + 8.0 * U * (ymax + c1)
+
+
+def band_sq(r, band_r):
+    """band_e of a squared residual."""
     return 2.0 * np.abs(r) * band_r + band_r * band_r + 4.0 * U * r * r
+
+
+def band_sum_sq(m, band_r, sr, sr2):
+    """The band of the sum of m squared residuals: sr = sum |r|, sr2 = sum r^2."""
+    return 2.0 * band_r * sr + m * band_r * band_r + (m + 4) * U * sr2
+
+
+def band_error(m, band_r, sr, sr2):
+    """The band of the mean squared error sr2 / m of a refit over m members."""
+    return band_sum_sq(m, band_r, sr, sr2) / m + 2.0 * U * (sr2 / m)
+
+
+def band_r2(m, ymax, band_r, sr2, sr, syy):
+    """(band_s, loose) of R^2 = 1 - sr2 / syy over m points, syy = sum (y - ybar)^2; loose: the denominator is not clearly
+    non-zero and R^2 is not trusted at all."""
+    e = 2.0 * (m + 4) * U * ymax
+    db = 2.0 * e * np.sqrt(m * syy) + m * e * e + (m + 4) * U * syy
+    loose = not syy > 4.0 * db
+    if sr2 == 0.0 or syy == 0.0:
+        return 0.0, loose
+    return 2.0 * (band_sum_sq(m, band_r, sr, sr2) + (sr2 / syy) * db) / syy, loose
 
 
 def restate_frame(points, init, dim, draws_of, points_per_fit=7, max_iters=100, fit_thresh=0.05, num_close_pts=10,
                   static_vel_thresh=0.2):
-    """One frame: dict(status, vel [dim], err, kept) and ``margin``, the smallest (distance from a decision) / (the kernel's band
+    """One frame: dict(status, vel [dim], err, kept; with an estimate also iter, the winning iteration, and members, its member
+    indices among the kept points; cond: the largest condition bound of a Gram matrix solved; margins: ``margin`` apart for the
+    static filter, the fit threshold and the choice among near-equal errors) and ``margin``, the smallest (distance from a decision) / (the kernel's band
     there) over every decision taken: above 1 the kernel has no reason to flag the frame.  ``draws_of(n)``: the
     ``[max_iters, points_per_fit]`` draws for n points.  Members are summed in ascending index order, and the systems are solved
     by ``np.linalg.solve``: neither is what the reference does."""
     pts = np.asarray(points, dtype=np.float64).reshape(-1, 4)
-    out = dict(status=0, vel=np.zeros(dim), err=0.0, kept=len(pts), margin=np.inf)
+    out = dict(status=0, vel=np.zeros(dim), err=0.0, kept=len(pts), margin=np.inf, cond=0.0,
+               margins=dict(static=np.inf, residual=np.inf, tie=np.inf))
     ymax = np.abs(pts[:, 3]).max() if len(pts) else 0.0
     if len(pts) >= num_close_pts and init is not None:
         r = pts[:, 3] + unit_rows(pts, dim) @ np.asarray(init, dtype=np.float64)
         e = r * r
-        band = _band_sq(r, 8.0 * U * (ymax + np.abs(init).sum()))
-        out["margin"] = min(out["margin"], (np.abs(e - static_vel_thresh) / band).min())
+        band = band_sq(r, band_residual(0.0, ymax, np.abs(init).sum()))
+        out["margins"]["static"] = (np.abs(e - static_vel_thresh) / band).min()
         pts = pts[e < static_vel_thresh]
     n = out["kept"] = len(pts)
     if n < num_close_pts:
+        out["margin"] = min(out["margins"].values())
         return out
     H, y = unit_rows(pts, dim), pts[:, 3]
     found = []
@@ -51,13 +87,14 @@ def restate_frame(points, init, dim, draws_of, points_per_fit=7, max_iters=100, 
         Hd, yd = H[drawn], y[drawn]
         G = Hd.T @ Hd
         c = np.linalg.solve(G, Hd.T @ yd)
-        scale = ymax + np.abs(c).sum()
-        band_r = 8.0 * (points_per_fit + 8) * U * _cond_bound(G) * scale + 8.0 * U * scale
+        c1 = np.abs(c).sum()
+        band_r = band_residual(band_coef(points_per_fit, cond_bound(G), ymax + c1), ymax, c1)
         r = y - H @ c
         e = r * r
         others = np.ones(n, dtype=bool)
         others[drawn] = False
-        out["margin"] = min(out["margin"], (np.abs(e - fit_thresh) / _band_sq(r, band_r))[others].min(initial=np.inf))
+        out["cond"] = max(out["cond"], cond_bound(G))
+        out["margins"]["residual"] = min(out["margins"]["residual"], (np.abs(e - fit_thresh) / band_sq(r, band_r))[others].min(initial=np.inf))
         member = ~others | (e < fit_thresh)
         m = int(member.sum())
         if m > num_close_pts:
@@ -66,16 +103,18 @@ def restate_frame(points, init, dim, draws_of, points_per_fit=7, max_iters=100, 
             c2 = np.linalg.solve(G, Hm.T @ ym)
             r = ym - Hm @ c2
             err = (r * r).sum() / m
-            scale = ymax + np.abs(c2).sum()
-            band_r = 8.0 * (m + 8) * U * _cond_bound(G) * scale + 8.0 * U * scale
-            band = (2.0 * band_r * np.abs(r).sum() + m * band_r * band_r + (m + 4) * U * (r * r).sum()) / m + 2.0 * U * err
+            c1 = np.abs(c2).sum()
+            out["cond"] = max(out["cond"], cond_bound(G))
+            band_r = band_residual(band_coef(m, cond_bound(G), ymax + c1), ymax, c1)
+            band = band_error(m, band_r, np.abs(r).sum(), (r * r).sum())
             found.append((err, it, c2, band, member))
     if found:
         err, it, c2, band, member = min(found, key=lambda t: (t[0], t[1]))
         for e2, it2, _, band2, member2 in found:
             if it2 != it and not np.array_equal(member, member2):
-                out["margin"] = min(out["margin"], (e2 - err) / (band + band2))
-        out.update(status=1, vel=-c2, err=float(err))
+                out["margins"]["tie"] = min(out["margins"]["tie"], (e2 - err) / (band + band2))
+        out.update(status=1, vel=-c2, err=float(err), iter=it, members=np.flatnonzero(member))
+    out["margin"] = min(out["margins"].values())
     return out
 
 
