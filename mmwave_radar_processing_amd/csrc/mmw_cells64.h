@@ -25,7 +25,7 @@
 // k_angle_argmax next to the list itself), so nothing is sorted.
 #pragma once
 #include "mmw_ctx.h"
-#include "mmw_misc.h"
+#include "mmw_argmax.h"
 #include "mmw_bf16x3.h"
 #include "mmw_cells64_mixed.h"
 

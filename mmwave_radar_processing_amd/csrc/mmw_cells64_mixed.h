@@ -1,5 +1,5 @@
 // What the dense float64 cell kernels share -- arguments, workgroup constants, LDS sizes, the plan predicate -- and
-// k_cells64_mixed<C>, the dense form for the chirp counts other than 128.  Included by mmw_cells64.h (k_cells64<128>, mmw_tu_misc.hip)
+// k_cells64_mixed<C>, the dense form for the chirp counts other than 128.  Included by mmw_cells64.h (k_cells64<128>, mmw_tu_points.hip)
 // and by mmw_tu_cells64.hip, which holds the instantiations of the mixed kernel: nothing here defines a non-template kernel, so
 // both translation units can take it.
 #pragma once

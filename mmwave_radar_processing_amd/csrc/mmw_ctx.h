@@ -410,7 +410,7 @@ inline int tune_int(const char *name, int dflt) {
     return v;
 }
 
-// an antenna list of a call (kernel argument; here because translation units without mmw_misc.h pass it too)
+// an antenna list of a call (kernel argument; here because translation units without mmw_argmax.h pass it too)
 constexpr int MAX_ANT = 32;
 struct AntList {
     int n;

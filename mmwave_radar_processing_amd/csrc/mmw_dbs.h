@@ -6,7 +6,7 @@
 //   out[f][s][i] = | sum_j hann(n)[j] RD[f][rx[j]][s][k_i] W_A^(j b_i) |,   b_i = (a_i - A/2) mod A  (the fftshift undone),
 // so the [A][S][C] cube behind it is never formed: n complex reads and n complex multiply-adds per pixel.
 #pragma once
-#include "mmw_misc.h"
+#include "mmw_ctx.h"
 
 namespace mmw {
 

@@ -35,7 +35,7 @@
 // tail over the cells this workgroup copied into the context's record list (DetectArgs::rec_cells, k_angle_argmax_recs).
 #pragma once
 #include "mmw_ctx.h"
-#include "mmw_misc.h"
+#include "mmw_argmax.h"
 #include "mmw_fft_fused.h"
 
 namespace mmw {
@@ -329,7 +329,7 @@ __device__ __forceinline__ void detect_argmax_lanes(const DetectArgs &a, const f
 
 // The stand-alone float32 argmax of mmw_angle_argmax_exact for lists of up to DET_MAX_ANT antennas, on the routine above (one
 // wave per detection, its cells in lanes, DPP reductions, W_A^m in the LDS, per-lane twiddles in registers, PD detections of
-// look-ahead).  k_angle_argmax (mmw_misc.h: cells n-fold in every lane's registers, global twiddle reads, shuffle butterflies)
+// look-ahead).  k_angle_argmax (mmw_argmax.h: cells n-fold in every lane's registers, global twiddle reads, shuffle butterflies)
 // took 1.16 us per 256 x 128 frame of ~470 OS-CFAR detections for the azimuth list alone.
 template <int NMAX>
 __global__ __launch_bounds__(256) void k_angle_argmax_lanes(const float2 *rd, const int32_t *dets, const int32_t *counts, int32_t *out_idx,

@@ -10,15 +10,29 @@ namespace mmw {
 // mmwgpu.hip
 int env_int(const char *name, int dflt);
 
-// mmw_tu_misc.hip
+// mmw_tu_input.hip
 bool fused_rd_ok(int S, int C);
+// the fused 256 x 128 range-Doppler kernel runs (range_doppler_impl's first choice)
+bool fused_rd_runs(int S, int C);
+// the range-Doppler stage touches no scratch: the fused kernel, or a compile-time mixed-radix one (tables only)
+bool rd_needs_no_scratch(int S, int C);
 // d_l1 != nullptr: also the per-plane L1 norms of the windowed input (mmw_plane_l1)
 int range_doppler_impl(mmw_ctx *ctx, const void *d_cubes, void *d_out, void *d_mag_f32, int n_frames, int V, int S, int C,
                        RawView rv = RawView{1, 0}, float *d_l1 = nullptr);
+// rounding-error budget of range_doppler_impl's float32 cells on an S x C plane, in units of 2^-24 of the plane's L1 norm
+int rd_error_ulps(int S, int C);
 int range_doppler_mag64_impl(mmw_ctx *ctx, const void *d_cubes, double *d_mag, int n_frames, int V, int S, int C, int rx_idx);
 // instantiated there for float and double
 template <typename T>
 int range_profile_impl(mmw_ctx *ctx, const void *d_cubes, T *d_out, int n_frames, int V, int S, int C, int chirp_idx);
+// d_out[f][s] = mean_v |d_spec[f][v][s]| on ctx->stream (k_mean_abs_over_v); instantiated there for float
+template <typename T>
+int mean_abs_over_v_impl(mmw_ctx *ctx, const void *d_spec, T *d_out, int n_frames, int V, int S);
+
+// mmw_tu_points.hip
+// the one-launch float64 |range-Doppler| plane of mmw_cells64.h (k_rd_mag64_256x128): the shape it exists for, and its launch
+bool rd_mag64_fused_ok(int S, int C);
+int launch_rd_mag64_fused(mmw_ctx *ctx, const void *d_cubes, double *d_mag, int n_frames, int V, int rx_idx);
 
 // mmw_tu_chain.hip
 int angle_fft_impl(mmw_ctx *ctx, const void *d_rd, void *d_out, int n_frames, int V, int S, int C, int A, int flags);

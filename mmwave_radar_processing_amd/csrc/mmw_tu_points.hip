@@ -1,315 +1,43 @@
-// Translation unit of every entry point whose kernels are in mmw_misc.h or in a header that includes it (mmw_dbs.h, mmw_detect.h,
-// mmw_cells64.h): input staging, the range-Doppler dispatch and its float64 plane, the range / Doppler-azimuth maps, the point-cloud
-// argmax with its float64 refinement, and mmw_detect_points.  One unit because those headers define plain (non-template) kernels:
-// a second unit that included any of them would define the same kernels again.
+// Translation unit of the point cloud: the per-detection angle argmax with its float64 refinement (mmw_argmax.h), the dense float64
+// cells (mmw_cells64.h) and mmw_detect_points (mmw_detect.h).
 #include "mmw_entry.h"
 #include "mmw_launch.h"
-#include "mmw_misc.h"
-#include "mmw_dbs.h"
-#include "mmw_czt.h"
+#include "mmw_argmax.h"
 #include "mmw_detect.h"
 #include "mmw_cells64.h"
 
 #include <algorithm>
-#include <climits>
-#include <cstdlib>
 
 using namespace mmw;
 
-bool mmw::fused_rd_ok(int S, int C) { return rd_fused_supported(S, C); }
+// ------------------------------------------------------------------ float64 |range-Doppler| of 256 x 128 planes (range_doppler_mag64_impl)
+bool mmw::rd_mag64_fused_ok(int S, int C) { return S == R64_S && C == R64_C; }
 
-namespace {
-
-// the fused 256 x 128 range-Doppler kernel runs (range_doppler_impl's first choice)
-bool fused_rd_runs(int S, int C) { return fused_rd_ok(S, C) && !env_int("MMW_NO_FUSED_RD", 0); }
-// the range-Doppler stage touches no scratch: the fused kernel, or a compile-time mixed-radix one (tables only)
-bool rd_needs_no_scratch(int S, int C) {
-    return fused_rd_runs(S, C) || (!fused_rd_ok(S, C) && rd_mixed_ct_supported(S, C) && !env_int("MMW_NO_MIXED_RD", 0));
-}
-
-int abs_c64(mmw_ctx *ctx, const void *d_in, float *d_out, size_t n) {
-    if (n == 0) return MMW_OK;
-    hipLaunchKernelGGL(k_abs_c64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const float2 *)d_in, d_out, n);
-    return check_launch("abs_c64");
-}
-
-// Range FFT (windows on both axes folded into the load) then in-place Doppler FFT + fftshift.
-// Frames go through in chunks of ~96 MB of output so that the Doppler pass finds the range
-// pass's result still in the 256 MB Infinity Cache instead of re-reading it from HBM.
-static int range_doppler_generic_chunk(mmw_ctx *ctx, const void *d_cubes, void *d_out, int F, int V, int S, int C) {
-    FftArgs a{};
-    a.in = d_cubes;
-    a.out = d_out;
-    a.outer = F * V;
-    a.inner = C;
-    a.n_in = S;
-    a.in_outer_stride = a.out_outer_stride = (long)S * C;
-    a.in_axis_stride = a.out_axis_stride = C;
-    a.in_inner_stride = a.out_inner_stride = 1;
-    MMW_TRY(get_table<float>(ctx, TAB_HANN, S, &a.win_axis));
-    MMW_TRY(get_table<float>(ctx, TAB_HANN, C, &a.win_inner));
-    a.scale = 1.0;
-    MMW_TRY((launch_fft_axis<float, float>(ctx, a, S, false)));
-    FftArgs b{};
-    b.in = d_out;
-    b.out = d_out;  // each workgroup reads its rows completely before it writes them
-    b.outer = F * V * S;
-    b.inner = 1;
-    b.n_in = C;
-    b.in_outer_stride = b.out_outer_stride = C;
-    b.in_axis_stride = b.out_axis_stride = 1;
-    b.scale = 1.0;
-    b.shift = 1;
-    return launch_fft_axis<float, float>(ctx, b, C, true);
-}
-
-int range_doppler_generic(mmw_ctx *ctx, const void *d_cubes, void *d_out, int F, int V, int S, int C) {
-    const size_t cube_bytes = (size_t)V * S * C * sizeof(float2);
-    long chunk = (long)(((size_t)96 << 20) / cube_bytes);
-    if (chunk < 1) chunk = 1;
-    for (long f0 = 0; f0 < F; f0 += chunk) {
-        const int nf = (int)((F - f0 < chunk) ? F - f0 : chunk);
-        MMW_TRY(range_doppler_generic_chunk(ctx, (const char *)d_cubes + (size_t)f0 * cube_bytes,
-                                            (char *)d_out + (size_t)f0 * cube_bytes, nf, V, S, C));
-    }
-    return MMW_OK;
-}
-
-}  // namespace
-
-template <typename T>
-int mmw::range_profile_impl(mmw_ctx *ctx, const void *d_cubes, T *d_out, int n_frames, int V, int S, int C,
-                            int chirp_idx) {
-    MMW_REQUIRE(ctx && d_cubes && d_out, "null argument");
-    MMW_JOIN(ctx);
-    MMW_REQUIRE(n_frames >= 0 && V > 0 && S > 0 && C > 0, "bad shape");
-    MMW_REQUIRE(chirp_idx >= -C && chirp_idx < C, "chirp_idx %d out of range", chirp_idx);
-    if (chirp_idx < 0) chirp_idx += C;  // numpy negative indexing
-    if (n_frames == 0) return MMW_OK;
-    MMW_TRY(ensure_scratch(ctx, (size_t)n_frames * V * S * sizeof(cplx<T>)));
-    FftArgs a{};
-    a.in = (const cplx<float> *)d_cubes + chirp_idx;
-    a.out = ctx->scratch;
-    a.outer = n_frames * V;
-    a.inner = 1;
-    a.n_in = S;
-    a.in_outer_stride = (long)S * C;
-    a.in_axis_stride = C;
-    a.in_inner_stride = 1;
-    a.out_outer_stride = S;
-    a.out_axis_stride = 1;
-    a.out_inner_stride = 1;
-    MMW_TRY(get_table<T>(ctx, TAB_HANN, S, &a.win_axis));
-    a.scale = 1.0;
-    MMW_TRY((launch_fft_axis<T, float>(ctx, a, S, false)));
-    const long n = (long)n_frames * S;
-    hipLaunchKernelGGL((k_mean_abs_over_v<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const cplx<T> *)ctx->scratch, d_out, n_frames, V, S);
-    return check_launch("mean_abs_over_v");
-}
-template int mmw::range_profile_impl<float>(mmw_ctx *, const void *, float *, int, int, int, int, int);
-template int mmw::range_profile_impl<double>(mmw_ctx *, const void *, double *, int, int, int, int, int);     // also mmw_tu_cfar.hip's
-
-static int plane_l1_impl(mmw_ctx *ctx, const void *d_cubes, float *d_l1, int n_frames, int V, int S, int C) {
-    if (n_frames == 0) return MMW_OK;
-    const void *ws, *wc;
-    MMW_TRY(get_table<float>(ctx, TAB_HANN, S, &ws));
-    MMW_TRY(get_table<float>(ctx, TAB_HANN, C, &wc));
-    ProfScope ps(ctx, "plane_l1");
-    hipLaunchKernelGGL(k_plane_l1, dim3((unsigned)(n_frames * V)), dim3(256), 0, ctx->stream, (const float2 *)d_cubes, d_l1, S,
-                       C, (const float *)ws, (const float *)wc);
-    return check_launch("plane_l1");
-}
-
-// ------------------------------------------------------------------ range-Doppler dispatch
-// rv.ntx > 1: d_cubes is the raw [F][num_rx][S][num_tx * C] cube and the virtual-array de-interleave is folded into
-// the load of the single-pass kernels (V == rv.ntx * rv.nrx).
-// d_l1 != nullptr: also the per-plane L1 norms of the windowed input (mmw_plane_l1), from inside the RD kernel where it
-// can produce them, else by a pass of k_plane_l1.
-int mmw::range_doppler_impl(mmw_ctx *ctx, const void *d_cubes, void *d_out, void *d_mag_f32, int n_frames, int V, int S, int C,
-                            RawView rv, float *d_l1) {
-    MMW_REQUIRE(ctx && d_cubes && d_out, "null argument");
-    MMW_REQUIRE(n_frames >= 0 && V > 0 && S > 0 && C > 0, "bad shape");
-    if (n_frames == 0) return MMW_OK;
-    {
-        ProfScope ps(ctx, "rd");
-        bool l1_done = false;
-        // int16 raw cubes: folded into the loads of the 256 x 128 kernel and of the compile-time mixed-radix kernels (the
-        // plane shapes of every shipped cfg); anything else converts + de-interleaves first (one extra pass)
-        const bool i16_folded = rv.i16 && rv.ntx > 1 &&
-                                (fused_rd_runs(S, C) ||
-                                 (rd_mixed_ct_supported(S, C) && !env_int("MMW_NO_MIXED_RD", 0)));
-        if (rv.i16 && !i16_folded) {
-            MMW_REQUIRE(rv.ntx >= 1 && rv.nrx >= 1, "int16 cubes are raw cubes");
-            const long total = (long)n_frames * V * S * C;
-            hipLaunchKernelGGL(k_reformat_i16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                               (const short2 *)d_cubes, (float2 *)d_out, total, rv.nrx, rv.ntx, S, C);
-            MMW_TRY(check_launch("reformat_i16"));
-            // every kernel below may run in place on a virtual-array cube: a workgroup has read all of its plane (and a
-            // persistent one prefetches only planes it will write itself) before it stores
-            d_cubes = d_out;
-            rv = RawView{1, 0, rv.vskip, 0};
-        }
-        if (fused_rd_runs(S, C))
-            MMW_TRY(launch_rd_fused(ctx, d_cubes, d_out, n_frames * V, S, C, rv, rv.ntx > 1 ? nullptr : d_l1, &l1_done));
-        else if (rd_lds_supported(S, C) && !env_int("MMW_NO_FUSED_RD", 0) && !rd_mixed_ct_supported(S, C))      // the compile-time kernel is faster where both exist (64 x 64: 6.0 vs 4.4 TB/s)
-            MMW_TRY(launch_rd_lds(ctx, d_cubes, d_out, n_frames * V, S, C, rv));
-        else if (rd_mixed_ct_supported(S, C) && !env_int("MMW_NO_MIXED_RD", 0)) {
-            // compile-time kernel; on virtual-array cubes it also leaves the planes' L1 norms when asked
-            float *l1 = rv.ntx > 1 ? nullptr : d_l1;
-            MMW_TRY(launch_rd_mixed_ct(ctx, d_cubes, (long)S * C, d_out, n_frames * V, S, C, rv, nullptr, 0, nullptr, false, l1));
-            l1_done = l1 != nullptr;
-        } else if (rd_mixed_supported(S, C) && !env_int("MMW_NO_MIXED_RD", 0))
-            MMW_TRY((launch_rd_mixed<float, false>(ctx, d_cubes, (long)S * C, d_out, n_frames * V, S, C, rv)));
-        else if (rv.ntx <= 1 && rd_split_ct_supported(S, C) && !env_int("MMW_NO_SPLIT_RD", 0))
-            MMW_TRY(launch_rd_split_ct(ctx, d_cubes, d_out, n_frames * V, S, C, rv));
-        else if (rv.ntx > 1) {
-            // no single-pass kernel for this plane: de-interleave into the output buffer, then transform it in place
-            const long total = (long)n_frames * V * S * C;
-            hipLaunchKernelGGL(k_reformat, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                               (const float2 *)d_cubes, (float2 *)d_out, total, rv.nrx, rv.ntx, S, C);
-            MMW_TRY(check_launch("reformat"));
-            // (the split kernel reads its whole plane before its first store, so it may run in place as well)
-            if (rd_split_ct_supported(S, C) && !env_int("MMW_NO_SPLIT_RD", 0))
-                MMW_TRY(launch_rd_split_ct(ctx, d_out, d_out, n_frames * V, S, C, RawView{1, 0, rv.vskip}));
-            else
-                MMW_TRY(range_doppler_generic(ctx, d_out, d_out, n_frames, V, S, C));
-        } else
-            MMW_TRY(range_doppler_generic(ctx, d_cubes, d_out, n_frames, V, S, C));
-        if (d_l1 && !l1_done) {
-            MMW_REQUIRE(rv.ntx <= 1, "plane L1 norms are defined on virtual-array cubes");
-            MMW_TRY(plane_l1_impl(ctx, d_cubes, d_l1, n_frames, V, S, C));
-        }
-    }
-    if (d_mag_f32) MMW_TRY(abs_c64(ctx, d_out, (float *)d_mag_f32, (size_t)n_frames * V * S * C));
-    return MMW_OK;
-}
-
-// Does the float64 CFAR plane of an S x C shape go through the LDS-resident single-pass kernel?  Every plane that fits in
-// float64 except small power-of-two ones, where the two-kernel register-FFT path is as fast (64 x 64, 512 x 8: equal;
-// 128 x 64, 256 x 32: single pass +18 %).  One predicate for range_doppler_mag64_impl and mmw_diag_rd_plan.
-static bool rd64_takes_mixed(int S, int C, RdMixedPlan *out) {
-    RdMixedPlan mp;
-    if (is_pow2(S) && is_pow2(C) && (long)S * C < 8192) return false;
-    if (env_int("MMW_NO_MIXED_RD", 0) || !rd_mixed_plan(S, C, sizeof(cplx<double>), &mp)) return false;
-    if (out) *out = mp;
-    return true;
-}
-
-int mmw::range_doppler_mag64_impl(mmw_ctx *ctx, const void *d_cubes, double *d_mag, int n_frames, int V, int S, int C,
-                                  int rx_idx) {
-    MMW_REQUIRE(ctx && d_cubes && d_mag, "null argument");
-    MMW_REQUIRE(n_frames >= 0 && V > 0 && S > 0 && C > 0 && rx_idx >= 0 && rx_idx < V, "bad shape / rx_idx");
-    if (n_frames == 0) return MMW_OK;
-    ProfScope ps(ctx, "rd64");
-    if (S == R64_S && C == R64_C && n_frames >= 8 && opt_int(ctx, "MMW_RD64_FUSED", 1)) {
-        // one launch, the complex128 intermediate in per-workgroup scratch that never leaves the caches (mmw_cells64.h); a whole
-        // frame per workgroup: batches only (a single frame is spread over the chip by the two generic launches)
-        const int grid = std::min(n_frames, ctx->num_cu);
-        MMW_TRY(ensure_scratch(ctx, (size_t)grid * S * C * sizeof(cplx<double>)));
-        Rd64Args ra{};
-        ra.cubes = (const float2 *)d_cubes + (long)rx_idx * S * C;
-        ra.frame_stride = (long)V * S * C;
-        ra.mag = d_mag;
-        ra.scratch = (cplx<double> *)ctx->scratch;
-        ra.n_frames = n_frames;
-        const void *p;
-        MMW_TRY(get_table<double>(ctx, TAB_HANN, S, &p));
-        ra.ws = (const double *)p;
-        MMW_TRY(get_table<double>(ctx, TAB_HANN, C, &p));
-        ra.wc = (const double *)p;
-        MMW_TRY(get_table<double>(ctx, TAB_TWIDDLE, S, &p));
-        ra.twS = (const cplx<double> *)p;
-        MMW_TRY(get_table<double>(ctx, TAB_TWIDDLE, C, &p));
-        ra.twC = (const cplx<double> *)p;
-        const size_t lds = rd64_lds();
-        MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rd_mag64_256x128), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_rd_mag64_256x128, dim3((unsigned)grid), dim3(C64_NT), lds, ctx->stream, ra);
-        return check_launch("rd_mag64_256x128");
-    }
-    if (rd64_takes_mixed(S, C, nullptr))
-        return launch_rd_mixed<double, true>(ctx, (const cplx<float> *)d_cubes + (long)rx_idx * S * C,
-                                             (long)V * S * C, d_mag, n_frames, S, C);
-    // two passes with a complex128 intermediate: chunks of frames small enough for the intermediate to stay in the
-    // Infinity Cache between them (128 MB; it also bounds the scratch: all 1250 frames of the bench at once were 640 MB)
-    const size_t plane_bytes = (size_t)S * C * sizeof(cplx<double>);
-    long chunk = (long)(((size_t)128 << 20) / plane_bytes);
-    if (chunk < 1) chunk = 1;
-    if (chunk > n_frames) chunk = n_frames;
-    MMW_TRY(ensure_scratch(ctx, (size_t)chunk * plane_bytes));
-    FftArgs a{};
-    a.out = ctx->scratch;
-    a.inner = C;
-    a.n_in = S;
-    a.in_outer_stride = (long)V * S * C;
-    a.out_outer_stride = (long)S * C;
-    a.in_axis_stride = a.out_axis_stride = C;
-    a.in_inner_stride = a.out_inner_stride = 1;
-    MMW_TRY(get_table<double>(ctx, TAB_HANN, S, &a.win_axis));
-    MMW_TRY(get_table<double>(ctx, TAB_HANN, C, &a.win_inner));
-    a.scale = 1.0;
-    FftArgs b{};
-    b.in = ctx->scratch;
-    b.inner = 1;
-    b.n_in = C;
-    b.in_outer_stride = b.out_outer_stride = C;
-    b.in_axis_stride = b.out_axis_stride = 1;
-    b.scale = 1.0;
-    b.shift = 1;
-    b.magnitude = 1;
-    for (long f0 = 0; f0 < n_frames; f0 += chunk) {
-        const int nf = (int)std::min<long>(chunk, n_frames - f0);
-        a.in = (const cplx<float> *)d_cubes + (f0 * V + rx_idx) * (long)S * C;
-        a.outer = nf;
-        MMW_TRY((launch_fft_axis<double, float>(ctx, a, S, false)));
-        b.out = d_mag + f0 * (long)S * C;
-        b.outer = nf * S;
-        MMW_TRY((launch_fft_axis<double, double>(ctx, b, C, true)));
-    }
-    return MMW_OK;
-}
-
-// ------------------------------------------------------------------ maps
-
-// Frames per launch pair (range-Doppler, k_dbs_sharpen) when the range-Doppler cubes go to the library's scratch: as many as keep
-// the intermediate within MMW_DBS_CHUNK_MB.  The default of 1024 bounds the scratch at 1 GB, as mmw_doppler_azimuth does; measured
-// on 1250 frames of 12 x 256 x 128 (tools/dbs_batch.py) larger chunks are faster all the way: 32 MB 3.82 ms, 128 MB
-// 2.46 ms, 1024 MB 2.07 ms, one chunk 2.04 ms -- keeping the chunk inside the Infinity Cache buys nothing against fewer launches.
-static long dbs_chunk_frames(const mmw_ctx *ctx, size_t cube_bytes, int n_frames) {
-    const size_t budget = (size_t)std::max(1, opt_int(ctx, "MMW_DBS_CHUNK_MB", 1024)) << 20;
-    return std::max<long>(1, std::min<long>({(long)(budget / cube_bytes), 65535L, (long)n_frames}));
-}
-
-// |angle FFT| averaged over the range rows [s_lo, s_hi): d_rd [nf][V][S][C] c64 -> d_out [nf][C][A] float32.
-// Fused single pass (k_angle64_rmean) when the angle fast path applies, else |angle FFT| cube + k_mean_over_range.
-// d_work: scratch of angle_mean_work_bytes(...) bytes.
-static size_t angle_mean_work_bytes(int nf, int V, int S, int C, int A, int rows) {
-    const bool fused = A == 64 && (V == 4 || V == 8 || V == 12 || V == 16) && !env_int("MMW_NO_FUSED_ANGLE", 0);
-    if (fused) return (size_t)nf * rmean_partitions(nf, S, C, rows) * RMEAN_RL * 64 * C * sizeof(float);
-    return (size_t)nf * A * S * C * sizeof(float);
-}
-
-static int angle_mean_impl(mmw_ctx *ctx, const void *d_rd, void *d_work, size_t work_bytes, float *d_out, int nf, int V,
-                           int S, int C, int A, int s_lo, int s_hi, int flags) {
-    const bool window = !(flags & MMW_ANGLE_NO_WINDOW), shift = !(flags & MMW_ANGLE_NO_SHIFT);
-    const bool fused = A == 64 && (V == 4 || V == 8 || V == 12 || V == 16) && !env_int("MMW_NO_FUSED_ANGLE", 0);
-    if (fused) {
-        ProfScope ps(ctx, "angle_rmean");
-        float h[16];
-        for (int i = 0; i < V; ++i) h[i] = window ? (float)np_window(TAB_HANN, i, V) : 1.f;
-        switch (V) {
-            case 4: return launch_angle64_rmean<4>(ctx, d_rd, (float *)d_work, work_bytes, d_out, nf, S, C, s_lo, s_hi, h, shift);
-            case 8: return launch_angle64_rmean<8>(ctx, d_rd, (float *)d_work, work_bytes, d_out, nf, S, C, s_lo, s_hi, h, shift);
-            case 12: return launch_angle64_rmean<12>(ctx, d_rd, (float *)d_work, work_bytes, d_out, nf, S, C, s_lo, s_hi, h, shift);
-            default: return launch_angle64_rmean<16>(ctx, d_rd, (float *)d_work, work_bytes, d_out, nf, S, C, s_lo, s_hi, h, shift);
-        }
-    }
-    MMW_TRY(angle_fft_impl(ctx, d_rd, d_work, nf, V, S, C, A, (flags & (MMW_ANGLE_NO_WINDOW | MMW_ANGLE_NO_SHIFT)) | MMW_ANGLE_MAGNITUDE));
-    const long total = (long)nf * A * C;
-    hipLaunchKernelGGL(k_mean_over_range, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const float *)d_work, d_out, nf, A, S, C, s_lo, s_hi);
-    return check_launch("mean_over_range");
+// one launch, the complex128 intermediate in per-workgroup scratch that never leaves the caches (mmw_cells64.h); a whole
+// frame per workgroup
+int mmw::launch_rd_mag64_fused(mmw_ctx *ctx, const void *d_cubes, double *d_mag, int n_frames, int V, int rx_idx) {
+    constexpr int S = R64_S, C = R64_C;
+    const int grid = std::min(n_frames, ctx->num_cu);
+    MMW_TRY(ensure_scratch(ctx, (size_t)grid * S * C * sizeof(cplx<double>)));
+    Rd64Args ra{};
+    ra.cubes = (const float2 *)d_cubes + (long)rx_idx * S * C;
+    ra.frame_stride = (long)V * S * C;
+    ra.mag = d_mag;
+    ra.scratch = (cplx<double> *)ctx->scratch;
+    ra.n_frames = n_frames;
+    const void *p;
+    MMW_TRY(get_table<double>(ctx, TAB_HANN, S, &p));
+    ra.ws = (const double *)p;
+    MMW_TRY(get_table<double>(ctx, TAB_HANN, C, &p));
+    ra.wc = (const double *)p;
+    MMW_TRY(get_table<double>(ctx, TAB_TWIDDLE, S, &p));
+    ra.twS = (const cplx<double> *)p;
+    MMW_TRY(get_table<double>(ctx, TAB_TWIDDLE, C, &p));
+    ra.twC = (const cplx<double> *)p;
+    const size_t lds = rd64_lds();
+    MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rd_mag64_256x128), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_rd_mag64_256x128, dim3((unsigned)grid), dim3(C64_NT), lds, ctx->stream, ra);
+    return check_launch("rd_mag64_256x128");
 }
 
 // ------------------------------------------------------------------ point cloud
@@ -360,44 +88,6 @@ static void launch_angle_argmax(mmw_ctx *ctx, dim3 grid, const float2 *rd, const
     else if (ants.n <= 16) MMW_ARGMAX(16);
     else MMW_ARGMAX(32);
 #undef MMW_ARGMAX
-}
-
-// Rounding-error budget of the float32 range-Doppler cell values, in units of eps = 2^-24 of the plane's L1 norm
-// (|rd32 - rd64| <= ulps * eps * sum |w x|), for whichever kernel range_doppler_impl runs on an S x C plane.
-//   windows: two products with table values, <= 8.
-//   structured transforms (k_rd_fused_256x128, k_rd_lds, k_rd_mixed_ct, k_rd_split2_ct: RegFFT / RegDFT levels): per
-//     prime factor p of the axis length one twiddle / inter-level product (complex FMA product + table value, <= 4) plus
-//     p == 2: the butterfly's add (inside the 4);  odd p: the real-symmetric form of RegDFT -- pair sums (1), a
-//     (p - 1) / 2-term FMA chain with literal coefficients ((p + 1) / 2), the +- i combine (1): <= (p + 7) / 2 + 1.
-//     The 127-point level of 63 x 127 / 127 x 32 / 254 x 50 is that form on MFMA tiles (64-term exact FMA chains).
-//   run-time mixed-radix kernel: its levels may be direct R-term chains: R per level on top.
-//   generic path: radix-2 levels (4 each) for powers of two, an N-term direct sum (N + 4) otherwise.
-// tests/test_rd_bound_cases_host.py restates these counts; tests/test_gpu_rd_error_bound.py asserts the inequality per family.
-static int rd_error_ulps(int S, int C) {
-    auto factors = [](int n) {
-        int u = 0;
-        for (int p = 2; n > 1; ++p)
-            while (n % p == 0) {
-                u += 4 + (p == 2 ? 0 : (p == 127 ? 88 : (p + 7) / 2 + 1));       // (127: the bfloat16 x 3 MFMA form, mmw_fft_mixed_ct.h)
-                n /= p;
-            }
-        return u;
-    };
-    const int structured = 8 + factors(S) + factors(C);
-    const bool no_fused = env_int("MMW_NO_FUSED_RD", 0), no_mixed = env_int("MMW_NO_MIXED_RD", 0);
-    if (!no_fused && (fused_rd_ok(S, C) || rd_lds_supported(S, C))) return structured;
-    if (!no_mixed && rd_mixed_ct_supported(S, C)) return structured;
-    RdMixedPlan mp;
-    if (!no_mixed && rd_mixed_plan(S, C, sizeof(cplx<float>), &mp))
-        return structured + mp.s1 + mp.s2 + mp.c1 + mp.c2 + 2 * (mp.rad_s[0] + mp.rad_s[1] + mp.rad_c[0] + mp.rad_c[1]);
-    if (rd_split_ct_supported(S, C) && !env_int("MMW_NO_SPLIT_RD", 0)) return structured;
-    int ulps = 8;
-    for (int axis = 0; axis < 2; ++axis) {
-        const int n = axis ? C : S;
-        if (is_pow2(n)) ulps += 4 * ilog2(n);
-        else ulps += n + 4;
-    }
-    return ulps;
 }
 
 // The launch of k_argmax_refine_part, shared by the refinement and by the read-out of its slices (mmw_rd_cells64_at): `units`
@@ -994,366 +684,6 @@ int detect_read_stats(DetectCall &d, int *h_stats) {
 
 extern "C" {
 
-// ------------------------------------------------------------------ input staging
-int mmw_synth_cubes(mmw_ctx *ctx, void *d_cubes, int n_frames, int V, int S, int C, uint64_t seed0,
-                    int num_targets, float noise_sigma) {
-    MMW_REQUIRE(ctx && d_cubes, "null argument");
-    MMW_JOIN(ctx);
-    MMW_REQUIRE(n_frames >= 0 && V > 0 && S > 0 && C > 0, "bad shape");
-    MMW_REQUIRE(num_targets >= 0 && num_targets <= SYNTH_MAX_TARGETS, "num_targets must be 0..%d", SYNTH_MAX_TARGETS);
-    const long total = (long)n_frames * V * S * C;
-    if (!total) return MMW_OK;
-    hipLaunchKernelGGL(k_synth, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (float2 *)d_cubes, total, V, S, C, (unsigned long long)seed0, num_targets, noise_sigma);
-    return check_launch("synth");
-}
-
-int mmw_virtual_array_reformat(mmw_ctx *ctx, const void *d_raw, void *d_virt, int n_frames, int num_rx,
-                               int num_tx, int S, int loops) {
-    MMW_REQUIRE(ctx && d_raw && d_virt, "null argument");
-    MMW_JOIN(ctx);
-    MMW_REQUIRE(n_frames >= 0 && num_rx > 0 && num_tx > 0 && S > 0 && loops > 0, "bad shape");
-    const long total = (long)n_frames * num_rx * num_tx * S * loops;
-    if (!total) return MMW_OK;
-    hipLaunchKernelGGL(k_reformat, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const float2 *)d_raw, (float2 *)d_virt, total, num_rx, num_tx, S, loops);
-    return check_launch("reformat");
-}
-
-int mmw_virtual_array_reformat_i16(mmw_ctx *ctx, const void *d_raw_i16, void *d_virt, int n_frames, int num_rx,
-                                   int num_tx, int S, int loops) {
-    MMW_REQUIRE(ctx && d_raw_i16 && d_virt, "null argument");
-    MMW_JOIN(ctx);
-    MMW_REQUIRE(n_frames >= 0 && num_rx > 0 && num_tx > 0 && S > 0 && loops > 0, "bad shape");
-    const long total = (long)n_frames * num_rx * num_tx * S * loops;
-    if (!total) return MMW_OK;
-    hipLaunchKernelGGL(k_reformat_i16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const short2 *)d_raw_i16, (float2 *)d_virt, total, num_rx, num_tx, S, loops);
-    return check_launch("reformat_i16");
-}
-
-int mmw_range_doppler(mmw_ctx *ctx, const void *d_cubes, void *d_out, void *d_mag_f32, int n_frames, int V,
-                      int S, int C) {
-    MMW_REQUIRE(ctx, "ctx is null");
-    MMW_JOIN(ctx);
-    return range_doppler_impl(ctx, d_cubes, d_out, d_mag_f32, n_frames, V, S, C);
-}
-
-int mmw_range_doppler_mag64(mmw_ctx *ctx, const void *d_cubes, double *d_mag, int n_frames, int V, int S,
-                            int C, int rx_idx) {
-    MMW_REQUIRE(ctx, "ctx is null");
-    MMW_JOIN(ctx);
-    return range_doppler_mag64_impl(ctx, d_cubes, d_mag, n_frames, V, S, C, rx_idx);
-}
-
-int mmw_range_profile(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C,
-                      int chirp_idx) {
-    return range_profile_impl<float>(ctx, d_cubes, d_out, n_frames, V, S, C, chirp_idx);
-}
-
-int mmw_range_profile_f64(mmw_ctx *ctx, const void *d_cubes, double *d_out, int n_frames, int V, int S, int C,
-                          int chirp_idx) {
-    return range_profile_impl<double>(ctx, d_cubes, d_out, n_frames, V, S, C, chirp_idx);
-}
-
-int mmw_range_zoom(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C, int chirp_idx,
-                   int m, double f0_cycles_per_sample, double df_cycles_per_sample) {
-    MMW_REQUIRE(ctx && d_cubes && d_out, "null argument");
-    MMW_JOIN(ctx);
-    MMW_REQUIRE(n_frames >= 0 && V > 0 && S > 0 && C > 0 && m > 0, "bad shape");
-    MMW_REQUIRE(chirp_idx >= -C && chirp_idx < C, "chirp_idx %d out of range", chirp_idx);
-    MMW_REQUIRE((size_t)S * sizeof(float2) <= 64 * 1024, "too many samples for the zoom DFT row buffer");
-    if (chirp_idx < 0) chirp_idx += C;
-    if (n_frames == 0) return MMW_OK;
-    const void *hann;
-    MMW_TRY(get_table<float>(ctx, TAB_HANN, S, &hann));
-    MMW_TRY(ensure_scratch(ctx, (size_t)n_frames * V * m * sizeof(float2)));
-    // rows = (frame, antenna): x[row][i] = cube[frame][v][i][chirp]
-    if (czt_length(S) > 0 && !env_int("MMW_ZOOM_DIRECT", 0)) {
-        std::vector<double> freq(m);
-        for (int k = 0; k < m; ++k) freq[k] = f0_cycles_per_sample + (double)k * df_cycles_per_sample;
-        const CztPlan *plan = nullptr;
-        MMW_TRY(czt_plan(ctx, freq.data(), m, S, &plan));
-        CztArgs z{};
-        z.x = (const float2 *)d_cubes + chirp_idx;
-        z.outer_stride = (long)S * C;
-        z.inner_stride = 0;
-        z.elem_stride = C;
-        z.s_lo = 0;
-        z.s_keep = 1;
-        z.win = (const float *)hann;
-        z.M = m;
-        z.rows = (long)n_frames * V;
-        z.out = (float2 *)ctx->scratch;
-        MMW_TRY(launch_czt_rows(ctx, *plan, z));
-    } else {
-        hipLaunchKernelGGL(k_zoom_dft, dim3(n_frames * V), dim3(256), (size_t)S * sizeof(float2), ctx->stream,
-                           (const float2 *)d_cubes + chirp_idx, (long)S * C, (long)C, (const float *)hann,
-                           (float2 *)ctx->scratch, S, m, f0_cycles_per_sample, df_cycles_per_sample);
-        MMW_TRY(check_launch("zoom_dft"));
-    }
-    const long n = (long)n_frames * m;
-    hipLaunchKernelGGL((k_mean_abs_over_v<float>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const cplx<float> *)ctx->scratch, d_out, n_frames, V, m);
-    return check_launch("mean_abs_over_v");
-}
-
-int mmw_range_angle(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C, int A,
-                    int chirp_idx, const int *h_rx, int n_rx, int perform_windowing) {
-    MMW_REQUIRE(ctx && d_cubes && d_out, "null argument");
-    MMW_JOIN(ctx);
-    MMW_REQUIRE(n_frames >= 0 && V > 0 && S > 0 && C > 0 && A > 0, "bad shape");
-    MMW_REQUIRE(chirp_idx >= -C && chirp_idx < C, "chirp_idx %d out of range", chirp_idx);
-    MMW_REQUIRE(n_rx >= 0 && (n_rx == 0 || h_rx), "bad rx list");
-    if (chirp_idx < 0) chirp_idx += C;
-    std::vector<int> rx;
-    if (n_rx == 0)
-        for (int v = 0; v < V; ++v) rx.push_back(v);
-    else
-        for (int i = 0; i < n_rx; ++i) {
-            int r = h_rx[i];
-            if (r < 0) r += V;
-            MMW_REQUIRE(r >= 0 && r < V, "rx index %d out of range", h_rx[i]);
-            rx.push_back(r);
-        }
-    const int n_sel = (int)rx.size();
-    MMW_REQUIRE(n_sel <= A, "more antennas (%d) than angle bins (%d)", n_sel, A);
-    if (n_frames == 0) return MMW_OK;
-    MMW_TRY(ensure_scratch(ctx, (size_t)n_frames * n_sel * S * sizeof(cplx<float>)));
-    for (int i = 0; i < n_sel; ++i) {
-        FftArgs a{};
-        a.in = (const cplx<float> *)d_cubes + (long)rx[i] * S * C + chirp_idx;
-        a.out = (cplx<float> *)ctx->scratch + (long)i * S;
-        a.outer = n_frames;
-        a.inner = 1;
-        a.n_in = S;
-        a.in_outer_stride = (long)V * S * C;
-        a.in_axis_stride = C;
-        a.in_inner_stride = 1;
-        a.out_outer_stride = (long)n_sel * S;
-        a.out_axis_stride = 1;
-        a.out_inner_stride = 1;
-        a.scale = 1.0;
-        if (perform_windowing) {
-            MMW_TRY(get_table<float>(ctx, TAB_HANN, S, &a.win_axis));
-            a.scale = np_window(TAB_HANN, rx[i], V);   // hann over ALL V antennas, then the subset
-        }
-        MMW_TRY((launch_fft_axis<float, float>(ctx, a, S, false)));
-    }
-    FftArgs b{};
-    b.in = ctx->scratch;
-    b.out = d_out;
-    b.outer = n_frames;
-    b.inner = S;
-    b.n_in = n_sel;
-    b.in_outer_stride = (long)n_sel * S;
-    b.in_axis_stride = S;
-    b.in_inner_stride = 1;
-    b.out_outer_stride = (long)S * A;
-    b.out_axis_stride = 1;
-    b.out_inner_stride = A;
-    b.scale = 1.0;
-    b.shift = 1;
-    b.magnitude = 1;
-    return launch_fft_axis<float, float>(ctx, b, A, false);
-}
-
-int mmw_dbs_gather(mmw_ctx *ctx, const float *d_mag, const int *h_ang_idx, const int *h_vel_idx, float *d_out,
-                   int n_frames, int A, int S, int C, int n_out) {
-    MMW_REQUIRE(ctx && d_mag && h_ang_idx && h_vel_idx && d_out, "null argument");
-    MMW_JOIN(ctx);
-    MMW_REQUIRE(n_frames >= 0 && A > 0 && S > 0 && C > 0 && n_out > 0, "bad shape");
-    for (int i = 0; i < n_out; ++i)
-        MMW_REQUIRE(h_ang_idx[i] >= 0 && h_ang_idx[i] < A && h_vel_idx[i] >= 0 && h_vel_idx[i] < C,
-                    "gather index %d out of range", i);
-    if (n_frames == 0) return MMW_OK;
-    MMW_TRY(ensure_scratch(ctx, (size_t)2 * n_out * sizeof(int)));
-    int *d_idx = (int *)ctx->scratch;
-    MMW_HIP(hipMemcpyAsync(d_idx, h_ang_idx, (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    MMW_HIP(hipMemcpyAsync(d_idx + n_out, h_vel_idx, (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    MMW_HIP(hipStreamSynchronize(ctx->stream));     // the index arrays are caller-owned host memory
-    const long total = (long)n_frames * S * n_out;
-    hipLaunchKernelGGL(k_dbs_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_mag, d_idx,
-                       d_idx + n_out, d_out, n_frames, A, S, C, n_out);
-    return check_launch("dbs_gather");
-}
-
-int mmw_dbs_sharpen(mmw_ctx *ctx, const void *d_cubes, void *d_rd, const int32_t *h_ang_idx, const int32_t *h_vel_idx,
-                    float *d_out, int n_frames, int V, int S, int C, int A, const int *h_rx, int n_rx, int n_out) {
-    MMW_REQUIRE(ctx, "ctx is null");
-    MMW_JOIN(ctx);
-    MMW_REQUIRE(n_frames >= 0 && V > 0 && S > 0 && C > 0 && A > 0 && n_out >= 0, "bad shape");
-    MMW_REQUIRE(n_rx >= 0 && (n_rx == 0 || h_rx), "bad rx list");
-    const int n = n_rx ? n_rx : V;
-    MMW_REQUIRE(n <= MAX_ANT, "antenna list of %d entries: at most %d", n, MAX_ANT);
-    MMW_REQUIRE(A >= n, "more antennas (%d) than angle bins (%d)", n, A);
-    for (int j = 0; j < n_rx; ++j)
-        MMW_REQUIRE(h_rx[j] >= 0 && h_rx[j] < V, "rx entry %d is %d: not an antenna of [0, %d)", j, h_rx[j], V);
-    if (n_frames == 0 || n_out == 0) return MMW_OK;
-    MMW_REQUIRE(d_cubes && h_ang_idx && h_vel_idx && d_out, "null argument");
-    MMW_REQUIRE((long)n_frames * S * n_out <= (long)INT_MAX, "%d frames of %d x %d pixels do not fit the kernel's 32-bit pixel index",
-                n_frames, S, n_out);
-    // (b_i, k_i) per frame and output: the FFT bin behind the fftshifted angle index, and the Doppler index as the cube stores it
-    std::vector<int2> tab((size_t)n_frames * n_out);
-    for (int f = 0; f < n_frames; ++f)
-        for (int i = 0; i < n_out; ++i) {
-            const size_t e = (size_t)f * n_out + i;
-            const int a = h_ang_idx[e], k = h_vel_idx[e];
-            MMW_REQUIRE(a >= 0 && a < A, "frame %d, entry %d: angle index %d is not in [0, %d)", f, i, a, A);
-            MMW_REQUIRE(k >= 0 && k < C, "frame %d, entry %d: Doppler index %d is not in [0, %d)", f, i, k, C);
-            tab[e] = make_int2(((a - A / 2) % A + A) % A, k);
-        }
-    DbsArgs da{};
-    da.V = V, da.S = S, da.C = C, da.A = A, da.n_out = n_out;
-    for (int j = 0; j < n; ++j) {       // np.hanning(n) over the SUBSET (process_dbs_enhanced :290-295); zero only at its two ends
-        const float w = (float)np_window(TAB_HANN, j, n);
-        if (w == 0.f) continue;
-        if (da.n_eff == 0) da.j0 = j;
-        da.ant[da.n_eff] = n_rx ? h_rx[j] : j;
-        da.w[da.n_eff++] = w;
-    }
-    MMW_TRY(get_table<float>(ctx, TAB_TWIDDLE, A, (const void **)&da.tw));
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t cube_bytes = (size_t)V * S * C * sizeof(float2), tab_bytes = up(tab.size() * sizeof(int2));
-    const long chunk = d_rd ? std::min(n_frames, 65535) : dbs_chunk_frames(ctx, cube_bytes, n_frames);
-    MMW_TRY(ensure_scratch(ctx, tab_bytes + (d_rd ? 0 : (size_t)chunk * cube_bytes)));
-    int2 *d_tab = (int2 *)ctx->scratch;
-    MMW_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
-    MMW_HIP(hipStreamSynchronize(ctx->stream));     // the table is host memory of this call
-    const bool tw_lds = (size_t)A * sizeof(float2) <= 32768;
-    const size_t lds = tw_lds ? (size_t)A * sizeof(float2) : 0;
-    const dim3 block(256);
-    for (long f0 = 0; f0 < n_frames; f0 += chunk) {
-        const int nf = (int)std::min<long>(chunk, n_frames - f0);
-        char *rd = d_rd ? (char *)d_rd + (size_t)f0 * cube_bytes : (char *)ctx->scratch + tab_bytes;
-        MMW_TRY(range_doppler_impl(ctx, (const char *)d_cubes + (size_t)f0 * cube_bytes, rd, nullptr, nf, V, S, C));
-        ProfScope ps(ctx, "dbs_sharpen");
-        da.rd = (const float2 *)rd;
-        da.tab = d_tab + (size_t)f0 * n_out;
-        da.out = d_out + (size_t)f0 * S * n_out;
-        const dim3 grid((unsigned)(((long)S * n_out + 255) / 256), (unsigned)nf);
-        if (tw_lds) hipLaunchKernelGGL(k_dbs_sharpen<true>, grid, block, lds, ctx->stream, da);
-        else hipLaunchKernelGGL(k_dbs_sharpen<false>, grid, block, 0, ctx->stream, da);
-        MMW_TRY(check_launch("dbs_sharpen"));
-    }
-    return MMW_OK;
-}
-
-int mmw_mean_over_range(mmw_ctx *ctx, const float *d_mag, float *d_out, int n_frames, int A, int S, int C,
-                        int s_lo, int s_hi) {
-    MMW_REQUIRE(ctx && d_mag && d_out, "null argument");
-    MMW_JOIN(ctx);
-    MMW_REQUIRE(n_frames >= 0 && A > 0 && S > 0 && C > 0, "bad shape");
-    MMW_REQUIRE(0 <= s_lo && s_lo < s_hi && s_hi <= S, "empty or out-of-range row interval [%d, %d)", s_lo, s_hi);
-    const long total = (long)n_frames * A * C;
-    if (!total) return MMW_OK;
-    hipLaunchKernelGGL(k_mean_over_range, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_mag, d_out,
-                       n_frames, A, S, C, s_lo, s_hi);
-    return check_launch("mean_over_range");
-}
-
-int mmw_doppler_azimuth(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C, int A,
-                        int s_lo, int s_hi, int flags) {
-    MMW_REQUIRE(ctx && d_cubes && d_out, "null argument");
-    MMW_JOIN(ctx);
-    MMW_REQUIRE(n_frames >= 0 && V > 0 && S > 0 && C > 0 && A >= V, "bad shape (need A >= V)");
-    MMW_REQUIRE(0 <= s_lo && s_lo < s_hi && s_hi <= S, "empty or out-of-range row interval [%d, %d)", s_lo, s_hi);
-    MMW_REQUIRE((flags & ~(MMW_ANGLE_NO_WINDOW | MMW_ANGLE_NO_SHIFT)) == 0, "unknown flag bits %d", flags);
-    if (n_frames == 0) return MMW_OK;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t cube_bytes = (size_t)V * S * C * sizeof(float2);
-    long chunk = std::min<long>(n_frames, 65535);
-    while (chunk > 1 && up(chunk * cube_bytes) + angle_mean_work_bytes((int)chunk, V, S, C, A, s_hi - s_lo) > ((size_t)1 << 30))
-        chunk = (chunk + 1) / 2;
-    const size_t work_bytes = angle_mean_work_bytes((int)chunk, V, S, C, A, s_hi - s_lo);
-    MMW_TRY(ensure_scratch(ctx, up(chunk * cube_bytes) + work_bytes));
-    char *d_rd = (char *)ctx->scratch, *d_work = d_rd + up(chunk * cube_bytes);
-    for (long f0 = 0; f0 < n_frames; f0 += chunk) {
-        const int nf = (int)std::min<long>(chunk, n_frames - f0);
-        MMW_TRY(range_doppler_impl(ctx, (const char *)d_cubes + (size_t)f0 * cube_bytes, d_rd, nullptr, nf, V, S, C));
-        MMW_TRY(angle_mean_impl(ctx, d_rd, d_work, work_bytes, d_out + (size_t)f0 * C * A, nf, V, S, C, A, s_lo, s_hi, flags));
-    }
-    return MMW_OK;
-}
-
-int mmw_doppler_azimuth_zoom(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C, int A,
-                             int s_lo, int s_hi, int n_used, const double *h_freq, int M, int flags) {
-    MMW_REQUIRE(ctx && d_cubes && d_out && h_freq, "null argument");
-    MMW_JOIN(ctx);
-    MMW_REQUIRE(n_frames >= 0 && V > 0 && S > 0 && C > 0 && A >= V && M > 0, "bad shape (need A >= V, M > 0)");
-    MMW_REQUIRE(0 <= s_lo && s_lo < s_hi && s_hi <= S, "empty or out-of-range row interval [%d, %d)", s_lo, s_hi);
-    MMW_REQUIRE(n_used > 0 && n_used <= C, "zoom transform defined for %d chirps, the cube has %d", n_used, C);
-    MMW_REQUIRE((flags & ~(MMW_ANGLE_NO_WINDOW | MMW_ANGLE_NO_SHIFT)) == 0, "unknown flag bits %d", flags);
-    constexpr int RB = 16;
-    MMW_REQUIRE((size_t)RB * n_used * sizeof(float2) <= 64 * 1024, "too many chirps for the zoom row buffer");
-    if (n_frames == 0) return MMW_OK;
-    ProfScope ps(ctx, "dopaz_zoom");
-    const int Sk = s_hi - s_lo;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_freq = up((size_t)M * sizeof(double)), b_tab = up((size_t)n_used * M * sizeof(float2));
-    const size_t f_rng = (size_t)V * S * C * sizeof(float2), f_zoom = (size_t)V * Sk * M * sizeof(float2);
-    long chunk = std::min<long>(n_frames, 65535);
-    auto need = [&](long c) { return up(c * f_rng) + up(c * f_zoom) + up(angle_mean_work_bytes((int)c, V, Sk, M, A, Sk)); };
-    while (chunk > 1 && need(chunk) > ((size_t)1 << 30)) chunk = (chunk + 1) / 2;    // <= 1 GiB of intermediates per pass
-    MMW_TRY(ensure_scratch(ctx, b_freq + b_tab + need(chunk)));
-    char *base = (char *)ctx->scratch;
-    double *d_freq = (double *)base;
-    float2 *d_tab = (float2 *)(base + b_freq);
-    char *d_rng = base + b_freq + b_tab;
-    char *d_zoom = d_rng + up((size_t)chunk * f_rng);
-    char *d_mag = d_zoom + up((size_t)chunk * f_zoom);
-    // chirp-z form (mmw_czt.h) unless the list has no usable plan; MMW_ZOOM_DIRECT=1 keeps the direct n_used x M table
-    const CztPlan *plan = nullptr;
-    if (czt_length(n_used) > 0 && !env_int("MMW_ZOOM_DIRECT", 0)) MMW_TRY(czt_plan(ctx, h_freq, M, n_used, &plan));
-    if (!plan) {
-        MMW_HIP(hipMemcpyAsync(d_freq, h_freq, (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        MMW_HIP(hipStreamSynchronize(ctx->stream));     // h_freq is caller-owned host memory
-        const long tab_n = (long)n_used * M;
-        hipLaunchKernelGGL(k_zoom_table, dim3((unsigned)((tab_n + 255) / 256)), dim3(256), 0, ctx->stream, d_freq, d_tab,
-                           n_used, M);
-        MMW_TRY(check_launch("zoom_table"));
-    }
-    for (long f0 = 0; f0 < n_frames; f0 += chunk) {
-        const int nf = (int)((n_frames - f0 < chunk) ? n_frames - f0 : chunk);
-        FftArgs a{};                                 // range FFT, Hann(S) x Hann(C) folded into the load
-        a.in = (const char *)d_cubes + (size_t)f0 * f_rng;
-        a.out = d_rng;
-        a.outer = nf * V;
-        a.inner = C;
-        a.n_in = S;
-        a.in_outer_stride = a.out_outer_stride = (long)S * C;
-        a.in_axis_stride = a.out_axis_stride = C;
-        a.in_inner_stride = a.out_inner_stride = 1;
-        MMW_TRY(get_table<float>(ctx, TAB_HANN, S, &a.win_axis));
-        MMW_TRY(get_table<float>(ctx, TAB_HANN, C, &a.win_inner));
-        a.scale = 1.0;
-        MMW_TRY((launch_fft_axis<float, float>(ctx, a, S, false)));
-        const long rows = (long)nf * V * Sk;
-        if (plan) {
-            CztArgs z{};
-            z.x = (const float2 *)d_rng;
-            z.outer_stride = (long)S * C;
-            z.inner_stride = C;
-            z.elem_stride = 1;
-            z.s_lo = s_lo;
-            z.s_keep = Sk;
-            z.M = M;
-            z.rows = rows;
-            z.out = (float2 *)d_zoom;
-            MMW_TRY(launch_czt_rows(ctx, *plan, z));
-        } else {
-            hipLaunchKernelGGL((k_zoom_rows<RB>), dim3((unsigned)((rows + RB - 1) / RB), (unsigned)((M + 255) / 256)), dim3(256),
-                               (size_t)RB * n_used * sizeof(float2), ctx->stream, (const float2 *)d_rng, d_tab,
-                               (float2 *)d_zoom, S, C, s_lo, Sk, n_used, M, rows);
-            MMW_TRY(check_launch("zoom_rows"));
-        }
-        // antenna window + zero-padded angle FFT + |.| on [nf][V][Sk][M] and the mean over the kept range bins
-        MMW_TRY(angle_mean_impl(ctx, d_zoom, d_mag, up(angle_mean_work_bytes((int)chunk, V, Sk, M, A, Sk)), d_out + (size_t)f0 * M * A, nf, V, Sk, M,
-                                A, 0, Sk, flags));
-    }
-    return MMW_OK;
-}
-
 int mmw_angle_argmax(mmw_ctx *ctx, const void *d_rd, const int32_t *d_dets, const int32_t *d_counts,
                      int32_t *d_idx, int n_frames, int V, int S, int C, int cap, const int *h_ant, int n_ant,
                      int A, int shift) {
@@ -1370,13 +700,6 @@ int mmw_angle_argmax(mmw_ctx *ctx, const void *d_rd, const int32_t *d_dets, cons
     launch_angle_argmax(ctx, grid, (const float2 *)d_rd, d_dets, d_counts, d_idx, V, S, C, cap, ants, A, shift,
                         (const float2 *)twA, ArgmaxRefine{});
     return check_launch("angle_argmax");
-}
-
-int mmw_plane_l1(mmw_ctx *ctx, const void *d_cubes, float *d_l1, int n_frames, int V, int S, int C) {
-    MMW_REQUIRE(ctx && d_cubes && d_l1, "null argument");
-    MMW_JOIN(ctx);
-    MMW_REQUIRE(n_frames >= 0 && V > 0 && S > 0 && C > 0 && (long)n_frames * V < (1L << 31), "bad shape");
-    return plane_l1_impl(ctx, d_cubes, d_l1, n_frames, V, S, C);
 }
 
 int mmw_angle_argmax_exact(mmw_ctx *ctx, const void *d_cubes, const float *d_l1, const void *d_rd, const int32_t *d_dets,
@@ -1561,45 +884,6 @@ int mmw_rd_cells64_at(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_dets, 
     return MMW_OK;
 }
 
-int mmw_abs_c64(mmw_ctx *ctx, const void *d_in, float *d_out, size_t n) {
-    MMW_REQUIRE(ctx && (n == 0 || (d_in && d_out)), "null argument");
-    MMW_JOIN(ctx);
-    return abs_c64(ctx, d_in, d_out, n);
-}
-
-int mmw_widen_f32_f64(mmw_ctx *ctx, const float *d_in, double *d_out, size_t n) {
-    MMW_REQUIRE(ctx && (n == 0 || (d_in && d_out)), "null argument");
-    MMW_JOIN(ctx);
-    if (n == 0) return MMW_OK;
-    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)ctx->num_cu * 16);
-    hipLaunchKernelGGL(k_widen_f32_f64, dim3(grid), dim3(256), 0, ctx->stream, d_in, d_out, n);
-    return check_launch("widen_f32_f64");
-}
-
-int mmw_diag_rd_plan(int S, int C, int float64, int plan[8]) {
-    MMW_REQUIRE(plan && S > 0 && C > 0, "bad argument");
-    for (int i = 0; i < 8; ++i) plan[i] = 0;
-    RdMixedPlan pl{};
-    if (float64)
-        plan[0] = rd64_takes_mixed(S, C, &pl) ? 2 : 3;       // (the entry's own test: MMW_NO_MIXED_RD included)
-    else if (fused_rd_ok(S, C))
-        plan[0] = 0;
-    else if (rd_lds_supported(S, C))
-        plan[0] = 1;
-    else
-        plan[0] = rd_mixed_plan(S, C, sizeof(cplx<float>), &pl) ? 2 : (rd_split_ct_supported(S, C) ? 4 : 3);
-    if (plan[0] == 2) {
-        plan[1] = pl.cls;
-        plan[2] = pl.big;
-        plan[3] = pl.s1;
-        plan[4] = pl.s2;
-        plan[5] = pl.c1;
-        plan[6] = pl.c2;
-        plan[7] = (int)pl.lds_bytes;
-    }
-    return MMW_OK;
-}
-
 int mmw_diag_cells64_plan(int S, int C, int plan[8]) {
     MMW_REQUIRE(plan && S > 0 && C > 0, "bad argument");
     for (int i = 0; i < 8; ++i) plan[i] = 0;
@@ -1631,30 +915,6 @@ int mmw_diag_detect_plan(int S, int C, int cfar_kind, int train_r, int train_d, 
     plan[6] = p.ct_window;
     plan[7] = rd_error_ulps(S, C);
     return MMW_OK;
-}
-
-int mmw_diag_czt_runs(const double *h_freq, int M, int n_used, int *h_runs, int cap, int *n_runs) {
-    MMW_REQUIRE(h_freq && n_runs && M > 0 && n_used > 0 && cap >= 0 && (cap == 0 || h_runs), "bad argument");
-    const int L = czt_length(n_used);
-    *n_runs = 0;
-    if (L <= 0) return MMW_OK;              // no chirp-z length for this many input points
-    const auto runs = czt_runs(h_freq, M, L - n_used + 1);
-    *n_runs = (int)runs.size();
-    for (int i = 0; i < *n_runs && i < cap; ++i) {          // (offset, length, filled with zeros) per run
-        h_runs[3 * i] = std::get<0>(runs[i]);
-        h_runs[3 * i + 1] = std::get<1>(runs[i]);
-        h_runs[3 * i + 2] = std::get<2>(runs[i]) ? 1 : 0;
-    }
-    return MMW_OK;
-}
-
-int mmw_diag_membw(mmw_ctx *ctx, const void *d_src, void *d_dst, size_t bytes, int mode, int blocks) {
-    MMW_REQUIRE(ctx && d_src && d_dst && bytes % 16 == 0 && mode >= 0 && mode <= 7, "bad argument");
-    MMW_JOIN(ctx);
-    if (blocks <= 0) blocks = ctx->num_cu * 8;
-    hipLaunchKernelGGL(k_diag_membw, dim3(blocks), dim3(256), 0, ctx->stream, (const diag_f4 *)d_src,
-                       (diag_f4 *)d_dst, bytes / 16, mode);
-    return check_launch("diag_membw");
 }
 
 }  // extern "C"

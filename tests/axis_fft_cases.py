@@ -13,7 +13,7 @@ impulse columns (frame 1).
 References: numpy complex128 for float32 outputs; for float64 outputs a direct DFT in np.longdouble with integer (n k) mod N
 twiddle indices, added as a tree over runs of 32 terms (dft_longdouble; checked against mpmath by the host test).
 
-Budget (the project's counting rule, rd_error_ulps in csrc/mmw_tu_misc.hip; not tuned to the kernels), per output cell:
+Budget (the project's counting rule, rd_error_ulps in csrc/mmw_tu_input.hip; not tuned to the kernels), per output cell:
 
     |got - ref| <= ulps * eps * l1,   l1 = sum of the windowed |re| + |im| along the transformed axes,
     eps = 2^-24 (float32 output) or 2^-53 (float64 output),

@@ -18,7 +18,7 @@ namespace mmw {
 int chain_settle(mmw_ctx *) { return MMW_OK; }      // mmw_tu_chain.hip's; only reached through a context with chain work pending
 template <> int launch_fft_axis<float, float>(mmw_ctx *, FftArgs, int, bool) { return MMW_ERR_HIP; }    // mmw_tu_generic.hip's; never reached
 }  // namespace mmw
-extern "C" int mmw_range_doppler(mmw_ctx *, const void *, void *, void *, int, int, int, int) { return MMW_ERR_HIP; }   // mmw_tu_misc.hip's; never reached
+extern "C" int mmw_range_doppler(mmw_ctx *, const void *, void *, void *, int, int, int, int) { return MMW_ERR_HIP; }   // mmw_tu_input.hip's; never reached
 
 static int fails = 0, calls = 0;
 #define CHECK(cond)                                                          \

@@ -1,6 +1,6 @@
 """Adversarial planes for the rounding-error bound of the float32 range-Doppler kernels, and its checker.
 
-The inequality under test (mmw_tu_misc.hip above launch_refine_part), for every cell of every plane:
+The inequality under test (rd_error_ulps in mmw_tu_input.hip, below range_doppler_impl), for every cell of every plane:
 
     |rd32[cell] - rd64[cell]|  <=  rd_error_ulps(S, C) * 2^-24 * l1(plane),     l1 = sum hann(S) hann(C) (|re| + |im|)
 

@@ -35,7 +35,7 @@ def gamma(n):
 
 
 def l1_tol_plane(S, C):
-    """k_plane_l1 (mmw_misc.h) adds non-negative terms, so every rounding is a relative error of the final sum and the depth of
+    """k_plane_l1 (mmw_staging.h) adds non-negative terms, so every rounding is a relative error of the final sum and the depth of
     the longest chain bounds it: per term two table values (hann(S), hann(C): 1 each), |re| + |im| (1), the product with hann(C)
     (1) and the row's product with hann(S) (1) = 5; a lane's row chain -- ceil(C / 128) steps of two additions for even C,
     ceil(C / 64) additions for odd C; its chain over rows s = wave, wave + 4, ...: ceil(S / 4) additions; six shuffle steps of

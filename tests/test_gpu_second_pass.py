@@ -305,7 +305,7 @@ def test_dense_argmax_list_past_the_first_trip(ctx, num_cu):
 
 
 def test_per_frame_argmax_kernels_past_128_detections(ctx):
-    """k_angle_argmax (mmw_misc.h; what mmw_angle_argmax runs) and k_angle_argmax_lanes (mmw_detect.h; the first pass of
+    """k_angle_argmax (mmw_argmax.h; what mmw_angle_argmax runs) and k_angle_argmax_lanes (mmw_detect.h; the first pass of
     mmw_angle_argmax_exact under MMW_ARGMAX_FORM=0) launch x = min(ceil(cap / 4), 32) workgroups of four waves per frame,
     one detection per wave (a cap on detections per frame, not a CU cap): a wave takes a second detection above 128 in
     ONE frame.  200 detections in frame 0, 9 in frame 1.
