@@ -686,6 +686,33 @@ int mmw_capon(mmw_ctx *ctx, const void *d_X, const double *h_thetas, float *d_ou
  *   n_frames == 0: MMW_OK, nothing written.  Profile family "range_snapshots". */
 int mmw_range_snapshots(mmw_ctx *ctx, const void *d_cubes, void *d_out, int n_frames, int V, int S, int C,
                         const int *h_rx, int n_rx, int r_lo, int r_hi, int perform_windowing);
+/* mmw_capon_doppler: the Doppler bin of every detection made on a Capon range-azimuth map, through the MVDR weights of its cell.
+ *   No upstream implementation exists; the definition is DESIGN.md 4.28.  d_X [F][n][R][K] complex64 are the
+ *   snapshots mmw_capon took (widened exactly to float64 here), d_dets[F][cap][2] int32 (row q of the window, angle index t) and
+ *   d_counts[F] what mmw_compact2d wrote for the map; h_thetas: the T angles of the map in radians, host memory, read during
+ *   the call.  Per detection, with R_q = X_q X_q^H / K + delta tr(X_q X_q^H / K) / n I and a_i = exp(-j pi i sin(theta_t)):
+ *       u = R_q^-1 a,  w = u / Re(a^H u),  y[k] = sum_i conj(w_i) X[i][q][k],  z = fftshift(DFT_K(h y)),
+ *   h = np.hanning(K) when doppler_window, else ones:  d_dop[F][cap] = the first index of max |z| (np.argmax), d_peak[F][cap] =
+ *   |z[dop]|, d_spec (NULL, or [F][cap][K]) = |z|, d_points (NULL, or [F][cap][4]) = (rng cos(theta_t), rng sin(theta_t), 0,
+ *   d_vel[dop]) with rng = d_range[q] (the R rows of the window) -- each product one round-to-nearest multiply, cos / sin of
+ *   h_thetas made by the host's C library.  d_range and d_vel [K] may be NULL when d_points is.
+ *   A row whose R_q is not positive definite (a Cholesky pivot <= 0 or not finite: an all-zero row, a NaN in the row) gives every
+ *   detection of it dop -1, peak NaN, a NaN spectrum and velocity NaN; a detection whose q or t is out of range gives the same
+ *   and a NaN position.  Counts are clamped to [0, cap]; slots past a frame's count are zeroed in every output.  The list may
+ *   hold its detections in any order.  One workgroup per (frame, row); rows without detections end after reading the list.
+ *   MMW_ERR_INVALID (nothing launched, outputs untouched; the text names what was refused): a null ctx, d_X, d_dets, d_counts,
+ *   h_thetas, d_dop or d_peak, d_points without d_range and d_vel, n_frames < 0, n outside 1..16, K outside 1..512, R, T or
+ *   cap < 1, a delta that is negative, NaN or infinite, a theta that is not finite.  MMW_ERR_UNSUPPORTED (nothing launched):
+ *   n_frames * R or n_frames * cap beyond 2^31 - 1.  n_frames == 0: MMW_OK, nothing written.  Profile family "capon_doppler".
+ * mmw_diag_capon_doppler_host: the same on host pointers (one implementation of the arithmetic, mmw_capon_doppler.h, and the
+ *   same order of every sum: the two agree bit for bit); no context, no device, nothing launched. */
+int mmw_capon_doppler(mmw_ctx *ctx, const void *d_X, const int32_t *d_dets, const int32_t *d_counts, const double *h_thetas,
+                      int32_t *d_dop, double *d_peak, double *d_spec, double *d_points, const double *d_range, const double *d_vel,
+                      int n_frames, int n, int R, int K, int T, int cap, double delta, int doppler_window);
+int mmw_diag_capon_doppler_host(const void *h_X, const int32_t *h_dets, const int32_t *h_counts, const double *h_thetas,
+                                int32_t *h_dop, double *h_peak, double *h_spec, double *h_points, const double *h_range,
+                                const double *h_vel, int n_frames, int n, int R, int K, int T, int cap, double delta,
+                                int doppler_window);
 
 /* ---------------------------------------------------------------- element-wise helpers */
 int mmw_abs_c64(mmw_ctx *ctx, const void *d_in, float *d_out, size_t n);

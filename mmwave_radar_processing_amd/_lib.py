@@ -136,6 +136,8 @@ _SIGNATURES = {
     "mmw_bartlett": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d],
     "mmw_capon": [_vp, _vp, C.POINTER(_d), _vp, _i, _i, _i, _i, _i, _d],
     "mmw_range_snapshots": [_vp, _vp, _vp, _i, _i, _i, _i, _ip, _i, _i, _i, _i],
+    "mmw_capon_doppler": [_vp, _vp, _vp, _vp, C.POINTER(_d), _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i],
+    "mmw_diag_capon_doppler_host": [_vp, _vp, _vp, C.POINTER(_d), _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i],
     "mmw_abs_c64":[_vp, _vp, _vp, _sz],
     "mmw_widen_f32_f64": [_vp, _vp, _vp, _sz],
     "mmw_diag_membw": [_vp, _vp, _vp, _sz, _i, _i],

@@ -17,9 +17,9 @@ from . import _lib
 from .detectors.base import BaseCFAR1D
 from .detectors.ca_cfar import CaCFAR2D
 from .processors.range_angle_resp import angle_tables
-from .processors.steering_beamformers import (CAPON_PASS_BUDGET, array_pattern_args, array_patterns,  # noqa: F401
-                                              array_patterns_on, capon_cube_args, capon_from_cubes, capon_pass_frames,
-                                              capon_passes)
+from .processors.steering_beamformers import (CAPON_PASS_BUDGET, CAPON_POINTS_PASS_FRAMES, array_pattern_args,  # noqa: F401
+                                              array_patterns, array_patterns_on, capon_cube_args, capon_doppler_on,
+                                              capon_from_cubes, capon_pass_frames, capon_passes, capon_points_args)
 
 
 def shard_bounds(n_frames: int, rank: int, world: int) -> Tuple[int, int]:
@@ -747,6 +747,95 @@ class FramePipeline:
         if self.n_frames == 0:
             return np.zeros(self._capon_shape)
         return d.download(self._capon_shape, np.float32).astype(np.float64)
+
+    def capon_point_clouds_device(self, thetas_rad, rx_antennas, detector, range_bins=None, delta: float = 1e-3,
+                                  perform_windowing: bool = True, doppler_windowing: bool = True,
+                                  frames_per_pass: Optional[int] = None) -> _lib.DeviceBuffer:
+        """The point clouds of ``capon_point_clouds`` left in HBM: a packed float64 ``[n_frames][det_capacity][4]`` buffer of
+        (x, y, z, velocity) rows, frame f holding its ``capon_counts[f]`` points first and zeros behind them.  The detections
+        (``d_capon_dets`` int32 ``[F][cap][2]`` (row of the window, angle index), ``d_capon_cnt``), their Doppler bins
+        (``d_capon_dop``) and peaks (``d_capon_peak``) and the float32 maps (``d_capon``) stay on the device too; the counts are
+        downloaded (``capon_counts``) and a frame with more detections than ``det_capacity`` raises as ``detect()`` does."""
+        # every argument check comes before the first use of self.ctx / self.bufs
+        th, rx, (r_lo, r_hi), delta, fpp, cfar, cap = capon_points_args(self.V, self.S, self.C, thetas_rad, rx_antennas, detector,
+                                                                        range_bins, delta, frames_per_pass, self.cap)
+        if len(self.range_bins) < r_hi or len(self.vel_bins) != self.C:
+            raise ValueError(f"capon_point_clouds: the config's {len(self.range_bins)} range bins / {len(self.vel_bins)} velocity bins "
+                             f"do not serve range bin {r_hi - 1} / {self.C} chirps (config and cube shape disagree)")
+        F, Rw, T, n, K = self.n_frames, r_hi - r_lo, len(th), len(rx), self.C
+        if fpp is None:
+            fpp = capon_pass_frames(n, Rw, K)
+        fpp = max(1, min(fpp, F, CAPON_POINTS_PASS_FRAMES))
+        lib, h, bufs, F1 = self.ctx.lib, self.ctx.handle, self.bufs, max(F, 1)
+        self._capon_shape = (F, Rw, T)
+        self.d_capon = bufs.get("capon_ra", F1 * Rw * T * 4)
+        d_snap = bufs.get("capon_snap", fpp * n * Rw * K * 8)
+        d_map64, d_mask = bufs.get("capon_map64", fpp * Rw * T * 8), bufs.get("capon_mask", fpp * Rw * T)
+        self.d_capon_dets, self.d_capon_cnt = bufs.get("capon_dets", F1 * cap * 8), bufs.get("capon_counts", F1 * 4)
+        self.d_capon_dop, self.d_capon_peak = bufs.get("capon_dop", F1 * cap * 4), bufs.get("capon_peak", F1 * cap * 8)
+        self.d_capon_points = bufs.get("capon_points", F1 * cap * 32)
+        rows = np.ascontiguousarray(self.range_bins[r_lo:r_hi], dtype=np.float64)
+        vel = np.ascontiguousarray(self.vel_bins, dtype=np.float64)
+        d_rng, d_vel = bufs.get("capon_range_tab", rows.nbytes), bufs.get("capon_vel_tab", vel.nbytes)
+        d_rng.upload(rows)          # float64 tables made on the host (no device libm)
+        d_vel.upload(vel)
+        kind, tr, ta, gr, ga, scale, k_rank = cfar
+        rx_arr, _ = _lib.int_array(rx)
+        th_ptr = th.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        for f0, f1 in capon_passes(F, fpp):
+            nf = f1 - f0
+            d_map = self.d_capon.at(f0 * Rw * T * 4)
+            _lib.check(lib.mmw_range_snapshots(h, self.d_in.at(f0 * self.cube_bytes), d_snap.ptr, nf, self.V, self.S, K, rx_arr, n,
+                                               r_lo, r_hi, int(bool(perform_windowing))))
+            _lib.check(lib.mmw_capon(h, d_snap.ptr, th_ptr, d_map, nf, n, Rw, K, T, delta))
+            _lib.check(lib.mmw_widen_f32_f64(h, d_map, d_map64.ptr, nf * Rw * T))
+            _lib.check(lib.mmw_cfar2d(h, d_map64.ptr, None, None, d_mask.ptr, nf, Rw, T, kind, tr, ta, gr, ga, scale, k_rank))
+            _lib.check(lib.mmw_compact2d(h, d_mask.ptr, self.d_capon_dets.at(f0 * cap * 8), self.d_capon_cnt.at(f0 * 4), nf, Rw, T, cap))
+            capon_doppler_on(self.ctx, d_snap.ptr, self.d_capon_dets.at(f0 * cap * 8), self.d_capon_cnt.at(f0 * 4), th,
+                             self.d_capon_dop.at(f0 * cap * 4), self.d_capon_peak.at(f0 * cap * 8), None,
+                             self.d_capon_points.at(f0 * cap * 32), d_rng.ptr, d_vel.ptr, nf, n, Rw, K, cap, delta, doppler_windowing)
+        self._capon_window = (r_lo, r_hi)
+        self.capon_counts = self.d_capon_cnt.download((F,), np.int32) if F else np.zeros(0, np.int32)
+        if np.any(self.capon_counts > cap):
+            raise _lib.MmwGpuError(f"detection capacity {cap} exceeded (max count {int(self.capon_counts.max())}): "
+                                   "raise det_capacity")
+        return self.d_capon_points
+
+    def capon_point_clouds(self, thetas_rad, rx_antennas, detector, range_bins=None, delta: float = 1e-3,
+                           perform_windowing: bool = True, doppler_windowing: bool = True,
+                           frames_per_pass: Optional[int] = None) -> List[np.ndarray]:
+        """Point clouds from the Capon / MVDR range-azimuth map of every resident frame: per-frame float64 ``(N, 4)`` arrays of
+        (x, y, z, velocity) rows (no upstream implementation exists; the definition is DESIGN.md 4.28).  Per frame: the map of
+        ``capon_range_angle`` as float64, ``detector`` (a stock ``CaCFAR2D`` / ``OsCFAR2D`` whose ``num_train`` / ``num_guard``
+        are (range, angle) pairs) on it, and for every detection (range bin r, angle index t), in ``detector.detect``'s
+        row-major order, the Doppler spectrum of the chirp sequence beamformed with the MVDR weights of that cell
+        (``CaponBeamformer.beamformed_doppler``; Hann over the chirps unless ``doppler_windowing=False``).  The point is
+        ``(rng cos(theta_t), rng sin(theta_t), 0, vel_bins[dop])`` with ``rng = range_bins[r]``: theta enters with the sign it
+        has in ``thetas_rad``, which puts a target on the side ``PointCloudGenerator``'s azimuth puts it for the same cube.  A
+        range row whose covariance is not positive definite (an all-zero row, a NaN) gives velocity NaN.
+
+        Sets ``capon_dets`` (per-frame int64 ``(N, 2)``: absolute range bin, angle index), ``capon_doppler_idx`` (int64 ``(N,)``,
+        -1 where the row is degenerate) and ``capon_peak`` (float64 ``(N,)``).  The returned lists are valid input to
+        ``ego_velocities(estimator, point_clouds=...)`` and ``vehicle_velocities(estimator, point_clouds=...)``.
+
+        Per pass of ``frames_per_pass`` frames (default ``capon_pass_frames``), on the context's queue in order and without a host
+        round trip: ``mmw_range_snapshots``, ``mmw_capon``, ``mmw_widen_f32_f64``, ``mmw_cfar2d`` (mask only),
+        ``mmw_compact2d``, ``mmw_capon_doppler``.  A frame's result does not depend on the pass it is in.  A frame with more
+        detections than ``det_capacity`` raises ``MmwGpuError`` as ``detect()`` does."""
+        d = self.capon_point_clouds_device(thetas_rad, rx_antennas, detector, range_bins, delta, perform_windowing,
+                                           doppler_windowing, frames_per_pass)
+        F, cap, counts, r_lo = self.n_frames, self.cap, self.capon_counts, self._capon_window[0]
+        if F == 0:
+            self.capon_dets, self.capon_doppler_idx, self.capon_peak = [], [], []
+            return []
+        pts = d.download((F, cap, 4), np.float64)
+        dets = self.d_capon_dets.download((F, cap, 2), np.int32)
+        dop = self.d_capon_dop.download((F, cap), np.int32)
+        peak = self.d_capon_peak.download((F, cap), np.float64)
+        self.capon_dets = [dets[f, :n].astype(np.int64) + np.array([r_lo, 0]) for f, n in enumerate(counts)]
+        self.capon_doppler_idx = [dop[f, :n].astype(np.int64) for f, n in enumerate(counts)]
+        self.capon_peak = [peak[f, :n].copy() for f, n in enumerate(counts)]
+        return [pts[f, :n].copy() if n else np.empty((0, 4)) for f, n in enumerate(counts)]
 
     def doppler_azimuth_device(self, proc, rx_sets, range_windows, shift_angle=True, precise_vel_ranges=None):
         """The maps of ``doppler_azimuth`` left in HBM, nothing downloaded: ``(buffer, (n_sets, F, rows, 64), m, bins)`` with the
@@ -2012,6 +2101,21 @@ class MultiDeviceFramePipeline:
                                                                         perform_windowing, frames_per_pass))
         maps = self._join([np.asarray(p, dtype=np.float64) for p in per_rank])
         return np.asarray(maps, dtype=np.float64).reshape(self.n_frames, r_hi - r_lo, len(th))
+
+    def capon_point_clouds(self, thetas_rad, rx_antennas, detector, range_bins=None, delta: float = 1e-3,
+                           perform_windowing: bool = True, doppler_windowing: bool = True,
+                           frames_per_pass: Optional[int] = None) -> List[np.ndarray]:
+        """``FramePipeline.capon_point_clouds`` of every shard on its own frames, joined in frame order (a frame's point cloud
+        does not depend on the other frames); ``capon_dets``, ``capon_doppler_idx`` and ``capon_peak`` are joined likewise."""
+        capon_points_args(self.shape[0], self.shape[1], self.shape[2], thetas_rad, rx_antennas, detector, range_bins, delta,
+                          frames_per_pass)
+        pcs = self._join(self._each(lambda r: self.parts[r].capon_point_clouds(
+            thetas_rad, rx_antennas, detector, range_bins, delta, perform_windowing, doppler_windowing, frames_per_pass)))
+        live = [p for r, p in enumerate(self.parts) if self.bounds[r][1] > self.bounds[r][0]]
+        self.capon_dets = self._join([p.capon_dets for p in live])
+        self.capon_doppler_idx = self._join([p.capon_doppler_idx for p in live])
+        self.capon_peak = self._join([p.capon_peak for p in live])
+        return pcs
 
     def doppler_azimuth(self, proc, rx_sets, range_windows, shift_angle=True, precise_vel_ranges=None):
         """``FramePipeline.doppler_azimuth`` of every shard on its rows of the per-frame tables, joined in frame order (the frames

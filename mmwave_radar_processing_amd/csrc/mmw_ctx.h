@@ -141,6 +141,8 @@ struct mmw_ctx {
     std::deque<mmw::CztPlan> czt_plans;         // (deque: pointers to cached plans survive later insertions)
     void *capon_z = nullptr;                    // exp(-j pi sin(theta_t)) of the last Capon angle grid ...
     std::vector<double> capon_key;              // ... and the grid it was built from
+    void *capon_dop_tab = nullptr;              // steering vectors [T][n], cos / sin of the angles (mmw_capon_doppler) ...
+    std::vector<double> capon_dop_key;          // ... and the grid and antenna count they were built from
 };
 
 namespace mmw {
@@ -155,13 +157,8 @@ inline double np_window(int kind, int i, int M) {
     return kind == TAB_HANN ? 0.5 + 0.5 * c : 0.54 + 0.46 * c;
 }
 
-template <typename T> int get_table(mmw_ctx *ctx, int kind, int N, const void **out) {
-    const auto key = std::make_tuple(kind, N, (int)(sizeof(T) == 8));
-    auto it = ctx->tables.find(key);
-    if (it != ctx->tables.end()) {
-        *out = it->second;
-        return MMW_OK;
-    }
+// The values of table (kind, N) as get_table uploads them (host memory only; mmw_diag_capon_doppler_host reads them here).
+template <typename T> std::vector<T> make_table(int kind, int N) {
     // DFTMAT rows are read up to 8 entries past the end by dft_level_big: zero padding
     const size_t elems = (kind == TAB_TWIDDLE) ? 2 * (size_t)N : (kind == TAB_DFTMAT ? 2 * ((size_t)N * N + 8) : (size_t)N);
     std::vector<T> h(elems, (T)0);
@@ -192,6 +189,18 @@ template <typename T> int get_table(mmw_ctx *ctx, int kind, int N, const void **
     } else {
         for (int i = 0; i < N; ++i) h[i] = (T)np_window(kind, i, N);
     }
+    return h;
+}
+
+template <typename T> int get_table(mmw_ctx *ctx, int kind, int N, const void **out) {
+    const auto key = std::make_tuple(kind, N, (int)(sizeof(T) == 8));
+    auto it = ctx->tables.find(key);
+    if (it != ctx->tables.end()) {
+        *out = it->second;
+        return MMW_OK;
+    }
+    const std::vector<T> h = make_table<T>(kind, N);
+    const size_t elems = h.size();
     void *d = nullptr;
     if (hipMalloc(&d, elems * sizeof(T)) != hipSuccess)
         return set_error(MMW_ERR_NOMEM, "hipMalloc(%zu) for table failed", elems * sizeof(T));

@@ -80,6 +80,7 @@ int mmw_ctx_destroy(mmw_ctx *ctx) {
     for (void *p : ctx->owned) (void)hipFree(p);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->capon_z) (void)hipFree(ctx->capon_z);
+    if (ctx->capon_dop_tab) (void)hipFree(ctx->capon_dop_tab);
     if (ctx->chain_ctl) (void)hipFree(ctx->chain_ctl);
     if (ctx->help_sync) (void)hipFree(ctx->help_sync);
     for (void *p : ctx->host_owned) (void)hipHostFree(p);

@@ -217,6 +217,56 @@ def capon_from_cubes(ctx: _lib.Context, d_cubes: int, d_snap: _lib.DeviceBuffer,
 
 C_POINTER_DOUBLE = C.POINTER(C.c_double)
 
+CAPON_DOPPLER_MAX_CHIRPS = 512      # include/mmwgpu.h mmw_capon_doppler: K of 1 .. 512
+CAPON_POINTS_PASS_FRAMES = 32768    # frames of one mmw_cfar2d call (its grid), so of one pass
+
+
+def capon_points_args(V: int, S: int, C_chirps: int, thetas_rad, rx_antennas, detector, range_bins=None, delta=1e-3,
+                      frames_per_pass=None, det_capacity: int = 2048):
+    """The argument checks of ``capon_point_clouds`` (no device is touched): those of ``capon_cube_args``, then the detector
+    and the capacity.  ``detector``: a stock ``CaCFAR2D`` / ``OsCFAR2D`` of this package whose ``num_train`` / ``num_guard`` are
+    (range, angle) pairs; it becomes (kind, train_r, train_a, guard_r, guard_a, scale, k_rank) the way ``FramePipeline(cfar=...)``
+    reads its detector.  Any other object raises ``ValueError``.  Returns ``(thetas float64 [T], rx list, (r_lo, r_hi), delta,
+    frames_per_pass or None, cfar tuple, cap)``."""
+    from ..detectors.base import BaseCFAR2D
+    th, rx, window, d, fpp = capon_cube_args(V, S, thetas_rad, rx_antennas, range_bins, delta, frames_per_pass)
+    what = "capon_point_clouds"
+    if not 1 <= int(C_chirps) <= CAPON_DOPPLER_MAX_CHIRPS:
+        raise ValueError(f"{what}: {C_chirps} chirps per frame (the beamformed Doppler spectrum takes 1 .. {CAPON_DOPPLER_MAX_CHIRPS})")
+    if not isinstance(detector, BaseCFAR2D) or type(detector)._compute_thresholds is not BaseCFAR2D._compute_thresholds or \
+            detector.kind not in (_lib.CFAR_CA, _lib.CFAR_OS):
+        raise ValueError(f"{what}: detector must be a stock CaCFAR2D or OsCFAR2D of this package, got {type(detector).__name__}")
+    pairs = []
+    for name in ("num_train", "num_guard"):
+        try:
+            a, b = getattr(detector, name)
+            ok = int(a) == a and int(b) == b and a >= 0 and b >= 0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{what}: detector.{name} must be a (range, angle) pair of non-negative integers, "
+                             f"got {getattr(detector, name)!r}")
+        pairs += [int(a), int(b)]
+    scale, k_rank = float(detector._scale()), int(detector._k_rank())
+    if not np.isfinite(scale):
+        raise ValueError(f"{what}: the detector's threshold factor {scale} is not finite")
+    if detector.kind == _lib.CFAR_OS:
+        n_train = (2 * (pairs[0] + pairs[2]) + 1) * (2 * (pairs[1] + pairs[3]) + 1) - (2 * pairs[2] + 1) * (2 * pairs[3] + 1)
+        if not 1 <= k_rank <= n_train:
+            raise ValueError(f"{what}: the detector's rank {k_rank} is not one of its {n_train} training cells")
+    if int(det_capacity) != det_capacity or int(det_capacity) < 1:
+        raise ValueError(f"{what}: det_capacity must be a positive integer, got {det_capacity}")
+    return th, rx, window, d, fpp, (int(detector.kind), *pairs, scale, k_rank), int(det_capacity)
+
+
+def capon_doppler_on(ctx: _lib.Context, d_X: int, d_dets: int, d_counts: int, thetas: np.ndarray, d_dop: int, d_peak: int,
+                     d_spec, d_points, d_range, d_vel, n_frames: int, n: int, R: int, K: int, cap: int, delta: float,
+                     doppler_windowing: bool) -> None:
+    """``mmw_capon_doppler`` on device addresses (``d_spec`` / ``d_points`` / ``d_range`` / ``d_vel`` may be None)."""
+    _lib.check(ctx.lib.mmw_capon_doppler(ctx.handle, d_X, d_dets, d_counts, thetas.ctypes.data_as(C_POINTER_DOUBLE), d_dop, d_peak,
+                                         d_spec, d_points, d_range, d_vel, n_frames, n, R, K, len(thetas), cap, delta,
+                                         int(bool(doppler_windowing))))
+
 
 class CaponBeamformer:
     """MVDR angle spectrum per range bin on a V-element half-wavelength ULA (no upstream oracle).
@@ -252,6 +302,63 @@ class CaponBeamformer:
         _lib.check(ctx.lib.mmw_capon(ctx.handle, d_X.ptr, th, d_out.ptr, F, V, R, K, T, self.delta))
         out = d_out.download((F, R, T), np.float32).astype(np.float64)
         return out[0] if single else out
+
+    def beamformed_doppler(self, X_vrk: np.ndarray, dets, doppler_windowing: bool = True, return_spectra: bool = False):
+        """The Doppler bin of detections made on ``process(X)``, each through the MVDR weights of its own cell (DESIGN.md 4.28,
+        ``mmw_capon_doppler``).  ``X [V, R, K]`` with ``dets`` an ``(N, 2)`` integer array of (row, angle index) ->
+        ``(dop int64 (N,), peak float64 (N,))``; a batch ``[F, V, R, K]`` with a list of F such arrays -> two lists.  Per
+        detection ``(q, t)``: ``w = R_q^-1 a / Re(a^H R_q^-1 a)`` with ``a = a(thetas_rad[t])``, ``y[k] = w^H X[:, q, k]``,
+        ``z = fftshift(fft(hanning(K) * y))`` (no window with ``doppler_windowing=False``), ``dop = argmax |z|``,
+        ``peak = |z[dop]|``.  ``return_spectra=True`` adds ``|z|`` as float64 ``(N, K)``.  A row whose loaded covariance is not
+        positive definite, and a detection outside the map, give ``dop`` -1 and ``peak`` NaN."""
+        X = np.ascontiguousarray(X_vrk, dtype=np.complex64)
+        single = X.ndim == 3
+        if single:
+            X, dets = X[None], [dets]
+        if X.ndim != 4:
+            raise ValueError("expected [V, R, K] or [F, V, R, K] snapshots")
+        F, V, R, K = X.shape
+        if len(dets) != F:
+            raise ValueError(f"beamformed_doppler: {len(dets)} detection lists for {F} frames")
+        lists = [np.asarray(d, dtype=np.int64).reshape(-1, 2) for d in dets]
+        for d in lists:
+            if d.size and (np.abs(d).max() >= 2**31):
+                raise ValueError("beamformed_doppler: a detection index does not fit int32")
+        if not 1 <= K <= CAPON_DOPPLER_MAX_CHIRPS:
+            raise ValueError(f"beamformed_doppler: {K} snapshots per bin (1 .. {CAPON_DOPPLER_MAX_CHIRPS})")
+        empty = (np.zeros(0, np.int64), np.zeros(0), np.zeros((0, K)))[:3 if return_spectra else 2]
+        cap = max([len(d) for d in lists] + [1])
+        if F == 0:
+            return ([], [], []) if return_spectra else ([], [])
+        if self._ctx is None:
+            self._ctx = _lib.default_context()
+        if self._bufs is None:
+            self._bufs = _lib.BufferSet(self._ctx)
+        ctx, bufs = self._ctx, self._bufs
+        packed = np.zeros((F, cap, 2), np.int32)
+        for f, d in enumerate(lists):
+            packed[f, :len(d)] = d
+        counts = np.array([len(d) for d in lists], np.int32)
+        d_X, d_dets, d_cnt = bufs.get("cap_x", X.nbytes), bufs.get("cd_dets", packed.nbytes), bufs.get("cd_cnt", counts.nbytes)
+        d_dop, d_peak = bufs.get("cd_dop", F * cap * 4), bufs.get("cd_peak", F * cap * 8)
+        d_spec = bufs.get("cd_spec", F * cap * K * 8) if return_spectra else None
+        d_X.upload(X)
+        d_dets.upload(packed)
+        d_cnt.upload(counts)
+        capon_doppler_on(ctx, d_X.ptr, d_dets.ptr, d_cnt.ptr, self.thetas_rad, d_dop.ptr, d_peak.ptr,
+                         d_spec.ptr if return_spectra else None, None, None, None, F, V, R, K, cap, self.delta, doppler_windowing)
+        dop = d_dop.download((F, cap), np.int32)
+        peak = d_peak.download((F, cap), np.float64)
+        spec = d_spec.download((F, cap, K), np.float64) if return_spectra else None
+        out = []
+        for f, n in enumerate(counts):
+            row = (dop[f, :n].astype(np.int64), peak[f, :n].copy()) if n else empty[:2]
+            if return_spectra:
+                row += (spec[f, :n].copy() if n else empty[2],)
+            out.append(row)
+        if single:
+            return out[0]
+        return tuple(list(col) for col in zip(*out))
 
     def process_cube(self, cube_vsc: np.ndarray, rx_antennas, range_bins=None, perform_windowing: bool = True) -> np.ndarray:
         """One radar cube ``[V, S, C]`` (samples on the slow axis, chirps contiguous) -> float64 ``[R_w, T]``; a batch
