@@ -472,7 +472,11 @@ int mmw_compact2d(mmw_ctx *ctx, const uint8_t *d_mask, int32_t *d_dets, int32_t 
  * mmw_cfar1d_gated: the 1-D CFAR of mmw_cfar1d (bit-identical decisions) along Doppler on the rows d_gate[f] = (near, far),
  *   both included, of each frame's d_mag64[F][R][D] (the reference's per-row vel_detector.detect, :110-120), then the ordered
  *   compaction of mmw_compact2d into d_dets[F][cap][2] / d_counts[F] (exact counts on overflow).  d_mask[F][R][D] is work
- *   space.  Context option MMW_GROUND_FLAG_ALL = 1: both candidate entries flag every frame / window (tests of the host path). */
+ *   space.  Context option MMW_GROUND_FLAG_ALL = 1: both candidate entries flag every frame / window (tests of the host path).
+ * mmw_diag_ground_pick: the picker of mmw_ground_candidates alone on a caller's d_profile[n_rows][S] float64 (linear values, one
+ *   workgroup per row), max_peaks 2 or 3: d_cand[n_rows][3] = d_bins[peak] in its first d_counts[row] slots (the others are not
+ *   written), d_counts[n_rows] as above, -1 included.  Refusals as mmw_ground_candidates (S >= 3, S <= 3072, n_rows <= 65535,
+ *   MMW_ERR_INVALID, nothing launched); honours MMW_GROUND_FLAG_ALL.  For tests of the picker's decisions. */
 int mmw_ground_candidates(mmw_ctx *ctx, const void *d_cubes, const double *d_bins, double *d_profile, double *d_cand,
                           int32_t *d_counts, int n_frames, int V, int S, int C);
 int mmw_ground_zoom_candidates(mmw_ctx *ctx, const void *d_cubes, const double *d_cand, const int32_t *d_counts,
@@ -481,6 +485,8 @@ int mmw_ground_zoom_candidates(mmw_ctx *ctx, const void *d_cubes, const double *
 int mmw_cfar1d_gated(mmw_ctx *ctx, const double *d_mag64, const int32_t *d_gate, uint8_t *d_mask, int32_t *d_dets,
                      int32_t *d_counts, int n_frames, int R, int D, int kind, int num_train, int num_guard, double scale,
                      int k_rank, int cap);
+int mmw_diag_ground_pick(mmw_ctx *ctx, const double *d_profile, const double *d_bins, double *d_cand, int32_t *d_counts,
+                         int n_rows, int S, int max_peaks);
 
 /* Batched RangeDopplerDetectorSequential (range_doppler_detection/range_doppler_detector_sequential.py:72-107 per frame;
  * the detector has no state across frames).  All CFAR arguments are those of mmw_cfar1d, decisions bit-identical to it.

@@ -107,9 +107,9 @@ __device__ __forceinline__ double linspace_bin(double lo, double hi, int k, int 
     return prod + lo;
 }
 
-// prof[f][S] float64 -> cand[f][3] = bins[peak] (strongest first), counts[f] (-1: the host decides)
+// prof[f][S] float64 -> cand[f][3] = bins[peak] (strongest first, at most max_peaks <= 3), counts[f] (-1: the host decides)
 __global__ __launch_bounds__(256) void k_ground_peaks(const double *prof, const double *bins, double *cand, int32_t *counts,
-                                                      int S, int flag_all) {
+                                                      int S, int max_peaks, int flag_all) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double *p = reinterpret_cast<double *>(smem), *y = p + S;
     __shared__ int list[PEAK_LIST];
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void k_ground_peaks(const double *prof, const 
         y[i] = 20.0 * log10(v);
     }
     __syncthreads();
-    const int n = pick_peaks(p, y, S, GROUND_COARSE, list, &n_list, top);
+    const int n = pick_peaks(p, y, S, max_peaks, list, &n_list, top);
     if (threadIdx.x < GROUND_COARSE && (int)threadIdx.x < n) cand[f * GROUND_COARSE + threadIdx.x] = bins[top[threadIdx.x]];
     if (threadIdx.x == 0) counts[f] = flag_all ? -1 : n;
 }

@@ -211,7 +211,23 @@ int mmw_ground_candidates(mmw_ctx *ctx, const void *d_cubes, const double *d_bin
     MMW_TRY(range_profile_impl<double>(ctx, d_cubes, d_profile, n_frames, V, S, C, 0));
     ProfScope ps(ctx, "ground");
     hipLaunchKernelGGL(k_ground_peaks, dim3(n_frames), dim3(256), (size_t)S * 2 * sizeof(double), ctx->stream, d_profile, d_bins,
-                       d_cand, d_counts, S, ground_flag_all(ctx));
+                       d_cand, d_counts, S, GROUND_COARSE, ground_flag_all(ctx));
+    return check_launch("ground_peaks");
+}
+
+// k_ground_peaks on a caller's profiles (tests/test_gpu_ground_pick.py): the picker alone, at either max_peaks the detector uses
+int mmw_diag_ground_pick(mmw_ctx *ctx, const double *d_profile, const double *d_bins, double *d_cand, int32_t *d_counts, int n_rows,
+                         int S, int max_peaks) {
+    MMW_REQUIRE(ctx && d_profile && d_bins && d_cand && d_counts, "null argument");
+    MMW_JOIN(ctx);
+    MMW_REQUIRE(n_rows >= 0 && n_rows <= 65535 && S >= 3, "bad shape");
+    MMW_REQUIRE(max_peaks == GROUND_FINE || max_peaks == GROUND_COARSE, "max_peaks is %d (%d or %d)", max_peaks, GROUND_FINE,
+                GROUND_COARSE);
+    MMW_REQUIRE((size_t)S * 2 * sizeof(double) <= 48 * 1024, "range profile of %d samples does not fit the picker's LDS", S);
+    if (n_rows == 0) return MMW_OK;
+    ProfScope ps(ctx, "ground");
+    hipLaunchKernelGGL(k_ground_peaks, dim3(n_rows), dim3(256), (size_t)S * 2 * sizeof(double), ctx->stream, d_profile, d_bins,
+                       d_cand, d_counts, S, max_peaks, ground_flag_all(ctx));
     return check_launch("ground_peaks");
 }
 

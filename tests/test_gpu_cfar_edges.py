@@ -23,7 +23,8 @@ the two np.partition returns is open), everything else bit for bit.
 
 1-D (mmw_cfar1d, k_cfar1d -> cfar1d_threshold): all four kinds, (T, G) up to num_train 512, five rows of 1301 cells in
 one call (rows straddle workgroups), rows of exactly one window and one cell short of it.  mmw_cfar1d_gated
-(k_cfar1d_gated + k_compact2d) with the gate over all rows, with and without capacity overflow.
+(k_cfar1d_gated + k_compact2d) with the gate over all rows, and with a gate of its own per frame (all rows, one row, empty, starting
+above the plane, ending below it; R * D a multiple of 256 and not), with and without capacity overflow.
 """
 import functools
 
@@ -246,6 +247,37 @@ def test_cfar1d_gated_matches_row_by_row(ctx, kind):
         try:
             bufs[0].upload(planes)
             bufs[1].upload(gate)
+            _lib.check(ctx.lib.mmw_cfar1d_gated(ctx.handle, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, bufs[4].ptr,
+                                                F, R, D, kind, T, G, 1.0, k, cap))
+            np.testing.assert_array_equal(bufs[2].download((F, R, D), np.uint8), mask_ref)
+            assert_compaction(bufs[3].download((F, cap, 2), np.int32), bufs[4].download((F,), np.int32), mask_ref, cap)
+        finally:
+            for b in bufs:
+                b.free()
+
+
+@pytest.mark.parametrize("shape", [cc.PLANE_A, (32, 72)], ids=["45x70", "32x72"])    # R * D = 3150 (12.3 workgroups) and 9 * 256
+@pytest.mark.parametrize("kind", [cc.CA, cc.OS, cc.GO, cc.SO])
+def test_cfar1d_gated_with_a_gate_of_its_own_per_frame(ctx, kind, shape):
+    """Five frames, five gates: all rows, one row, an empty gate (near > far), a gate that starts above the plane and one that
+    ends below it.  The mask is the row-by-row reference on the selected rows and 0 elsewhere, every cell written."""
+    T, G, (R, D), k = 3, 1, shape, (4 if kind == cc.OS else 0)
+    planes = np.stack([cc.quantised((R, D), 6, 41 + f) for f in range(4)] + [cc.nonfinite((R, D), 45, (0, T + G))[0]])
+    F = planes.shape[0]
+    gate = np.array([[0, R - 1], [3, 3], [5, 2], [-4, 1], [R - 2, R + 7]], np.int32)
+    mask_ref = np.zeros((F, R, D), np.uint8)
+    for f, (near, far) in enumerate(gate):
+        for r in range(max(near, 0), min(far, R - 1) + 1):
+            mask_ref[f, r] = cc.ref_cfar1d(planes[f, r], kind, T, G, 1.0, k)[2]
+    rows_hit = [sorted(set(np.where(m)[0])) for m in mask_ref]
+    assert not rows_hit[2] and rows_hit[1] == [3] and rows_hit[3] == [0, 1] and rows_hit[4] == [R - 2, R - 1] and len(rows_hit[0]) > 3
+    n_max = int(mask_ref.reshape(F, -1).sum(axis=1).max())
+    for cap in (R * D, n_max // 2):
+        bufs = [ctx.alloc(planes.nbytes), ctx.alloc(gate.nbytes), ctx.alloc(F * R * D), ctx.alloc(F * cap * 8), ctx.alloc(F * 4)]
+        try:
+            bufs[0].upload(planes)
+            bufs[1].upload(gate)
+            bufs[2].upload(np.full((F, R, D), 7, np.uint8))
             _lib.check(ctx.lib.mmw_cfar1d_gated(ctx.handle, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, bufs[4].ptr,
                                                 F, R, D, kind, T, G, 1.0, k, cap))
             np.testing.assert_array_equal(bufs[2].download((F, R, D), np.uint8), mask_ref)
