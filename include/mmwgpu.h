@@ -581,6 +581,26 @@ int mmw_detect_batch(mmw_ctx *ctx, const void *d_cubes, void *d_rd, double *d_ma
                      int32_t *d_dets, int32_t *d_counts, float *d_l1, int n_frames, int V, int S, int C, int cfar_kind,
                      int train_r, int train_d, int guard_r, int guard_d, double scale, int k_rank, int cap);
 
+/* Antenna-integrated (non-coherent) detection.  NO UPSTREAM IMPLEMENTATION: the reference's detectors threshold virtual
+ * antenna 0 alone; the definition is DESIGN.md 4.29 and is pinned by a NumPy restatement in the tests.
+ * mmw_range_doppler_power64: d_pow[F][S][C] float64 = sum over the n_ants antennas of h_ants (host memory, read during the
+ *   call), added in the order of the list, of re^2 + im^2 of the float64 plane mmw_range_doppler_mag64 is defined on,
+ *   fftshift_C( FFT_S FFT_C( hann(S) hann(C) x[f][v] ) ).  The order of the sum is the order of the list on every shape, so
+ *   one list gives the same bits from run to run; another order of the same antennas agrees to rounding only.  256 x 128
+ *   planes in batches of 8 frames and more: one persistent kernel, a frame (every listed antenna) per workgroup (the context
+ *   option MMW_POW64_FUSED = 0 turns it off); every other shape and batch: mmw_range_doppler_mag64's own pass per listed
+ *   antenna, each followed by d_pow (= | +=) |RD|^2.  Profile family "rd_pow64".
+ * mmw_detect_batch_integrated: mmw_detect_batch with that plane in the place of antenna 0's |RD|: d_rd and d_l1 as there,
+ *   d_pow[F][S][C] where mmw_detect_batch takes d_mag64, the 2-D CFAR (strict >) on d_pow, the ordered compaction.
+ *   MMW_ERR_INVALID (nothing launched, outputs untouched): a null ctx or buffer, a bad shape, h_ants NULL, n_ants outside
+ *   1 .. min(V, 32), an index outside [0, V), an index listed twice.  n_frames == 0: MMW_OK, nothing written. */
+int mmw_range_doppler_power64(mmw_ctx *ctx, const void *d_cubes, double *d_pow, int n_frames, int V, int S, int C,
+                              const int *h_ants, int n_ants);
+int mmw_detect_batch_integrated(mmw_ctx *ctx, const void *d_cubes, void *d_rd, double *d_pow, uint8_t *d_mask,
+                                int32_t *d_dets, int32_t *d_counts, float *d_l1, int n_frames, int V, int S, int C,
+                                int cfar_kind, int train_r, int train_d, int guard_r, int guard_d, double scale, int k_rank,
+                                int cap, const int *h_ants, int n_ants);
+
 /* mmw_detect_points: BASELINE configs[2] in one call -- range-Doppler of every antenna (float32, d_rd / d_l1 as above),
  *   CFAR on antenna 0, ordered detections and the azimuth / elevation argmax bins of every detection
  *   (range_doppler_detector.py:62-80, detectors/ca_cfar.py:85-155, point_cloud_generator.py:143-214), with the SAME

@@ -115,6 +115,8 @@ _SIGNATURES = {
     "mmw_cfar1d": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i],
     "mmw_compact2d": [_vp, _vp, _vp, _vp, _i, _i, _i, _i],
     "mmw_detect_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i],
+    "mmw_range_doppler_power64": [_vp, _vp, _vp, _i, _i, _i, _i, _ip, _i],
+    "mmw_detect_batch_integrated": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _ip, _i],
     "mmw_ground_candidates": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i],
     "mmw_ground_zoom_candidates": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d],
     "mmw_cfar1d_gated": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _i],

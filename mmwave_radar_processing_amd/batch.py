@@ -84,6 +84,27 @@ def _check_ground(ground, shape: Tuple[int, int, int]) -> None:
         raise ValueError(f"ground=: the detector's range tables do not have {S} bins (config and cube shape disagree)")
 
 
+def _check_integrate_rx(integrate_rx, V: int) -> List[int]:
+    """The antenna list of ``FramePipeline(integrate_rx=...)``: non-empty, ints in ``[0, V)``, each listed once."""
+    try:
+        items = list(integrate_rx)
+    except TypeError:
+        raise ValueError(f"integrate_rx= takes a list of antenna indices, got {type(integrate_rx).__name__}") from None
+    if not items:
+        raise ValueError("integrate_rx= must list at least one antenna")
+    for v in items:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"integrate_rx= takes ints, got {v!r}")
+        if not 0 <= int(v) < V:
+            raise ValueError(f"integrate_rx=: antenna {int(v)} is outside [0, {V})")
+    ants = [int(v) for v in items]
+    if len(set(ants)) != len(ants):
+        raise ValueError(f"integrate_rx=: an antenna is listed twice in {ants}")
+    if len(ants) > 32:
+        raise ValueError("integrate_rx=: at most 32 antennas")
+    return ants
+
+
 def _check_sequential(sequential) -> None:
     """What the batched sequential path serves: a RangeDopplerDetectorSequential whose two detectors are stock 1-D CFARs."""
     from .processors.range_doppler_detection.range_doppler_detector_sequential import RangeDopplerDetectorSequential
@@ -324,11 +345,22 @@ class FramePipeline:
 
     ``sequential=<RangeDopplerDetectorSequential>``: ``detect()`` / ``point_clouds()`` are those of
     ``PointCloudGenerator(detector_type="range_doppler_detector_sequential")`` called frame by frame.  Only the two CFAR
-    parameter sets of the detector are read (both stock 1-D CFARs); its per-frame caches are not touched."""
+    parameter sets of the detector are read (both stock 1-D CFARs); its per-frame caches are not touched.
+
+    ``integrate_rx=[v0, v1, ...]`` (no upstream counterpart): the 2-D CFAR of ``cfar=`` runs on the float64
+    power summed over the listed virtual antennas, ``sum_v |RD_v|^2`` added in list order, in place of antenna 0's ``|RD|``;
+    the angle estimates of the detections are unchanged.  Distinct ints in ``[0, V)``; not with ``ground=`` / ``sequential=``.
+    ``integrated_power()`` returns the plane.  ``None`` (the default): the reference's antenna-0 detection."""
 
     def __init__(self, config_manager, max_frames: int, shape: Tuple[int, int, int], num_angle_bins: int = 64,
                  cfar=None, az_antenna_idxs=(), el_antenna_idxs=(), shift_az_resp=True, shift_el_resp=False,
-                 det_capacity: int = 2048, ctx: _lib.Context = None, ground=None, sequential=None):
+                 det_capacity: int = 2048, ctx: _lib.Context = None, ground=None, sequential=None, integrate_rx=None):
+        self.integrate_rx = None
+        if integrate_rx is not None:
+            if ground is not None or sequential is not None:
+                raise ValueError("FramePipeline: integrate_rx= integrates the plane of the 2-D CFAR (cfar=); it cannot be "
+                                 "combined with ground= or sequential=")
+            self.integrate_rx = _check_integrate_rx(integrate_rx, int(shape[0]))
         if ground is not None:
             if cfar is not None:
                 raise ValueError("FramePipeline: pass either cfar= (2-D detection) or ground= (ground detector), not both")
@@ -1374,6 +1406,42 @@ class FramePipeline:
                                                  self.d_cnt.at(f0 * 4), self.d_l1.at(f0 * V * 4), nf, V, S, C, kind, tr, td, gr, gd,
                                                  scale, k_rank, cap))
 
+    def _detect_integrated(self, f0: int, nf: int):
+        """``_detect_float64`` with the power summed over ``integrate_rx`` as the CFAR plane (``mmw_detect_batch_integrated``)."""
+        V, S, C, cap = self.V, self.S, self.C, self.cap
+        n = S * C
+        self.d_pow = self.bufs.get("pow64", max(self.n_frames, 1) * n * 8)
+        d_mask = self.bufs.get("mask", max(self.n_frames, 1) * n)
+        kind, tr, td, gr, gd, scale, k_rank = self._cfar_args()
+        ants, n_ants = _lib.int_array(self.integrate_rx)
+        _lib.check(self.ctx.lib.mmw_detect_batch_integrated(
+            self.ctx.handle, self.d_in.at(f0 * self.cube_bytes), self.d_rd.at(f0 * self.cube_bytes), self.d_pow.at(f0 * n * 8),
+            d_mask.at(f0 * n), self.d_dets.at(f0 * cap * 8), self.d_cnt.at(f0 * 4), self.d_l1.at(f0 * V * 4), nf, V, S, C, kind,
+            tr, td, gr, gd, scale, k_rank, cap, ants, n_ants))
+
+    def integrated_power_device(self) -> _lib.DeviceBuffer:
+        """The CFAR plane of ``integrate_rx=``: float64 ``[F, S, C]`` in HBM, ``sum_v |RD_v|^2`` over the listed antennas in list
+        order (``mmw_range_doppler_power64``), computed from the resident cubes by this call."""
+        if self.integrate_rx is None:
+            raise ValueError("integrated_power: the pipeline was built without integrate_rx=")
+        F, n = self.n_frames, self.S * self.C
+        self.d_pow = self.bufs.get("pow64", max(F, 1) * n * 8)
+        ants, n_ants = _lib.int_array(self.integrate_rx)
+        for f0 in range(0, F, 32768):
+            _lib.check(self.ctx.lib.mmw_range_doppler_power64(self.ctx.handle, self.d_in.at(f0 * self.cube_bytes),
+                                                              self.d_pow.at(f0 * n * 8), min(32768, F - f0), self.V, self.S,
+                                                              self.C, ants, n_ants))
+        return self.d_pow
+
+    def integrated_power(self, lo: int = 0, hi: Optional[int] = None) -> np.ndarray:
+        """Frames ``[lo, hi)`` of ``integrated_power_device()`` on the host, float64 ``[hi - lo, S, C]``."""
+        buf = self.integrated_power_device()
+        lo, hi, _ = slice(lo, hi).indices(self.n_frames)
+        n = self.S * self.C
+        if hi <= lo:
+            return np.zeros((0, self.S, self.C))
+        return buf.download((hi - lo, self.S, self.C), np.float64, lo * n * 8)
+
     def _argmax_float64(self, d_idx, ant, shift, f0: int, nf: int):
         cap = self.cap
         arr, n_ant = _lib.int_array(ant)
@@ -1546,7 +1614,8 @@ class FramePipeline:
         return self.d_cnt.download((F,), np.int32)
 
     def detect(self) -> List[np.ndarray]:
-        """RD (all antennas, fp32) + CFAR on antenna 0 + ordered compaction for every frame.
+        """RD (all antennas, fp32) + CFAR on antenna 0 (with ``integrate_rx=``: on the power summed over the listed antennas) +
+        ordered compaction for every frame.
 
         Returns the per-frame int64 ``(N, 2)`` [range_idx, doppler_idx] arrays (row-major order, == np.where).  With
         ``ground=``: the ground detector's detections (gated rows, Doppler CFAR), and ``altitudes`` is set.  With
@@ -1562,6 +1631,10 @@ class FramePipeline:
             return self._detect_ground()
         if self.sequential is not None:
             return self._detect_sequential(False)
+        if self.integrate_rx is not None:
+            for f0 in range(0, F, 32768):
+                self._detect_integrated(f0, min(32768, F - f0))
+            return self.d_cnt.download((F,), np.int32)
         if self._fused_supported(False):
             return self._detect_fused(False)
         for f0 in range(0, F, 32768):       # grid limits of the per-frame launches
@@ -1581,7 +1654,7 @@ class FramePipeline:
         empty antenna list leaves None).  ``fetch``: also the host lists of ``detect()`` (``self.dets``).  Returns the counts."""
         self.n_refined = 0      # detections re-evaluated in float64 (near-ties of the float32 pass)
         self._alloc_detect()
-        if self.ground is None and self.sequential is None and self._fused_supported(True):
+        if self.ground is None and self.sequential is None and self.integrate_rx is None and self._fused_supported(True):
             counts = self._detect_fused(True)
             self._fetch_dets(counts) if fetch else self._check_capacity(counts)
             return counts
@@ -1999,6 +2072,16 @@ class MultiDeviceFramePipeline:
         self.dets = self._join([p.dets for p in live])
         self.n_refined = sum(p.n_refined for p in live)
         return pcs
+
+    def integrated_power(self) -> np.ndarray:
+        """``FramePipeline.integrated_power`` of every shard (``integrate_rx=`` among the pipeline keywords), joined in frame order:
+        float64 ``[F, S, C]``."""
+        _, S, C = self.shape
+        parts = self._each(lambda r: self.parts[r].integrated_power())
+        out = np.concatenate(parts) if parts else np.zeros((0, S, C))
+        if len(out) != self.n_frames:
+            raise RuntimeError(f"joined {len(out)} power planes for {self.n_frames} frames")
+        return out
 
     def ego_velocities(self, estimator) -> np.ndarray:
         """``FramePipeline.ego_velocities``: every device fits the frames of its shard (``ego_fits``), the estimator's state

@@ -11,9 +11,9 @@
 using namespace mmw;
 
 // ------------------------------------------------------------------ CFAR
-static int cfar2d_impl(mmw_ctx *ctx, const double *d_X, double *d_thr, double *d_noise, uint8_t *d_mask, int n_frames,
-                       int R, int D, int kind, int train_r, int train_d, int guard_r, int guard_d, double scale,
-                       int k_rank) {
+int mmw::cfar2d_impl(mmw_ctx *ctx, const double *d_X, double *d_thr, double *d_noise, uint8_t *d_mask, int n_frames,
+                     int R, int D, int kind, int train_r, int train_d, int guard_r, int guard_d, double scale,
+                     int k_rank) {
     MMW_REQUIRE(ctx && d_X, "null argument");
     MMW_REQUIRE(n_frames >= 0 && R > 0 && D > 0, "bad shape");
     MMW_REQUIRE(train_r >= 0 && train_d >= 0 && guard_r >= 0 && guard_d >= 0, "negative window size");
@@ -91,8 +91,8 @@ static int cfar2d_impl(mmw_ctx *ctx, const double *d_X, double *d_thr, double *d
     return check_launch("cfar2d");
 }
 
-static int compact2d_impl(mmw_ctx *ctx, const uint8_t *d_mask, int32_t *d_dets, int32_t *d_counts, int n_frames,
-                          int R, int D, int cap) {
+int mmw::compact2d_impl(mmw_ctx *ctx, const uint8_t *d_mask, int32_t *d_dets, int32_t *d_counts, int n_frames,
+                        int R, int D, int cap) {
     MMW_REQUIRE(ctx && d_mask && d_dets && d_counts, "null argument");
     MMW_REQUIRE(n_frames >= 0 && R > 0 && D > 0 && cap >= 0, "bad shape");
     if (n_frames == 0) return MMW_OK;

@@ -233,6 +233,17 @@ static bool rd64_takes_mixed(int S, int C, RdMixedPlan *out) {
     return true;
 }
 
+// Bytes of ctx->scratch range_doppler_mag64_impl below touches for n_frames planes of S x C (its three routes, restated): a caller
+// that keeps data of its own behind them sizes the scratch once, before the first launch (mmw_tu_integrated.hip).
+size_t mmw::rd_mag64_scratch_bytes(mmw_ctx *ctx, int n_frames, int S, int C) {
+    const size_t plane_bytes = (size_t)S * C * sizeof(cplx<double>);
+    if (rd_mag64_fused_ok(S, C) && n_frames >= 8 && opt_int(ctx, "MMW_RD64_FUSED", 1))
+        return (size_t)std::min(n_frames, ctx->num_cu) * plane_bytes;
+    if (rd64_takes_mixed(S, C, nullptr)) return 0;
+    const size_t chunk = std::max<size_t>(1, ((size_t)128 << 20) / plane_bytes);
+    return std::min<size_t>(chunk, (size_t)std::max(n_frames, 1)) * plane_bytes;
+}
+
 int mmw::range_doppler_mag64_impl(mmw_ctx *ctx, const void *d_cubes, double *d_mag, int n_frames, int V, int S, int C,
                                   int rx_idx) {
     MMW_REQUIRE(ctx && d_cubes && d_mag, "null argument");

@@ -88,6 +88,14 @@ def main():
     d_mag = ctx.alloc(F * S * C * 8)
     run("rd_mag64", lambda: _lib.check(L.mmw_range_doppler_mag64(ctx.handle, d_in.ptr, d_mag.ptr, F, V, S, C, 0)),
         F * (S * C * 8 + S * C * 8))
+    # antenna-integrated power plane over all V antennas (reads the whole cube, writes one float64 plane per frame): the
+    # persistent 256 x 128 kernel, and the per-antenna route (V one-antenna passes + d_pow += |RD|^2) on the same batch
+    all_v, n_all = _lib.int_array(range(V))
+    pow_call = lambda: _lib.check(L.mmw_range_doppler_power64(ctx.handle, d_in.ptr, d_mag.ptr, F, V, S, C, all_v, n_all))
+    run("rd_pow64_all_antennas", pow_call, F * (cube_b + S * C * 8))
+    ctx.set_option("MMW_POW64_FUSED", 0)
+    run("rd_pow64_all_antennas_per_antenna_route", pow_call, F * (cube_b + S * C * 8))
+    ctx.set_option("MMW_POW64_FUSED", None)
     d_thr, d_noise, d_mask = ctx.alloc(F * S * C * 8), ctx.alloc(F * S * C * 8), ctx.alloc(F * S * C)
     alpha = 144 * (1e-5 ** (-1.0 / 144) - 1.0)
     run("cfar2d_ca", lambda: _lib.check(L.mmw_cfar2d(ctx.handle, d_mag.ptr, d_thr.ptr, d_noise.ptr, d_mask.ptr, F, S, C,
