@@ -473,6 +473,10 @@ int mmw_compact2d(mmw_ctx *ctx, const uint8_t *d_mask, int32_t *d_dets, int32_t 
  *   both included, of each frame's d_mag64[F][R][D] (the reference's per-row vel_detector.detect, :110-120), then the ordered
  *   compaction of mmw_compact2d into d_dets[F][cap][2] / d_counts[F] (exact counts on overflow).  d_mask[F][R][D] is work
  *   space.  Context option MMW_GROUND_FLAG_ALL = 1: both candidate entries flag every frame / window (tests of the host path).
+ * mmw_cfar1d_rows: mmw_cfar1d_gated with the rows of frame f named by the ascending list d_rows[F][R] int32, first d_nrows[f]
+ *   entries (the lists of mmw_seq_rows; a length below 0 counts as 0, one above R as R; an entry outside [0, R) names no row),
+ *   in place of a gate: the second half of mmw_seq_detect_plane on a caller's plane.  Every cell of d_mask is written, 0 in
+ *   the rows that are not listed.
  * mmw_diag_ground_pick: the picker of mmw_ground_candidates alone on a caller's d_profile[n_rows][S] float64 (linear values, one
  *   workgroup per row), max_peaks 2 or 3: d_cand[n_rows][3] = d_bins[peak] in its first d_counts[row] slots (the others are not
  *   written), d_counts[n_rows] as above, -1 included.  Refusals as mmw_ground_candidates (S >= 3, S <= 3072, n_rows <= 65535,
@@ -485,6 +489,9 @@ int mmw_ground_zoom_candidates(mmw_ctx *ctx, const void *d_cubes, const double *
 int mmw_cfar1d_gated(mmw_ctx *ctx, const double *d_mag64, const int32_t *d_gate, uint8_t *d_mask, int32_t *d_dets,
                      int32_t *d_counts, int n_frames, int R, int D, int kind, int num_train, int num_guard, double scale,
                      int k_rank, int cap);
+int mmw_cfar1d_rows(mmw_ctx *ctx, const double *d_mag64, const int32_t *d_rows, const int32_t *d_nrows, uint8_t *d_mask,
+                    int32_t *d_dets, int32_t *d_counts, int n_frames, int R, int D, int kind, int num_train, int num_guard,
+                    double scale, int k_rank, int cap);
 int mmw_diag_ground_pick(mmw_ctx *ctx, const double *d_profile, const double *d_bins, double *d_cand, int32_t *d_counts,
                          int n_rows, int S, int max_peaks);
 
@@ -504,6 +511,9 @@ int mmw_diag_ground_pick(mmw_ctx *ctx, const double *d_profile, const double *d_
  *   the kernel needs 16 (S + C) + 25 * 4 * max(C, 256) bytes of LDS, at most 160 KiB (S <= 3072 with any C <= 512).
  * mmw_seq_detect_plane: the same result by the plain route: mmw_range_doppler_mag64 of antenna 0 into d_mag64[F][S][C], the
  *   kernel of mmw_cfar1d_gated on the listed rows (d_mask[F][S][C] is work space), mmw_compact2d.
+ * Row lists of both: d_nrows[f] below 0 counts as 0 and above S as S (d_rows holds S entries per frame); an entry outside
+ *   [0, S) names no row: it gives no detections and adds nothing to d_counts[f] (the d_rowmag entry of such a list position
+ *   is not defined).  Lists are ascending, as mmw_seq_rows writes them.
  * mmw_seq_route: 0 when FramePipeline(sequential=...) should call mmw_seq_detect, 1 for mmw_seq_detect_plane: the
  *   context option MMW_SEQ_FULL_PLANE (default 1: the full plane measured faster; 0 asks for the row
  *   kernel) or a shape the row kernel does not serve.  ctx may be NULL (environment and default only). */

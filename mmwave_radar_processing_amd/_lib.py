@@ -120,6 +120,7 @@ _SIGNATURES = {
     "mmw_ground_candidates": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i],
     "mmw_ground_zoom_candidates": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d],
     "mmw_cfar1d_gated": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _i],
+    "mmw_cfar1d_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _i],
     "mmw_diag_ground_pick": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i],
     "mmw_seq_rows": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i],
     "mmw_seq_detect": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _vp],

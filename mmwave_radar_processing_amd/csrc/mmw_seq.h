@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void k_seq_detect(SeqArgs a) {
 #pragma unroll
         for (int k = 0; k < SEQ_RPT; ++k) {
             slot[k] = q + k * parts;
-            const int v = slot[k] < nr ? rows[j0 + slot[k]] : 0;     // idle slots run row 0 and are dropped
+            const int v = slot[k] < nr ? rows[j0 + slot[k]] : 0;     // idle slots and entries outside [0, S) run row 0 and are dropped
             r[k] = (unsigned)v < (unsigned)S ? v : 0;
         }
         // range bins X[r, c] = sum_s hann(S)[s] x[0, s, c] W_S^(r s), in the order s = 0 .. S - 1
@@ -188,6 +188,7 @@ __global__ __launch_bounds__(256) void k_seq_detect(SeqArgs a) {
         if (tid < 64) {
             for (int j = 0; j < nr; ++j) {
                 const int rj = rows[j0 + j];
+                if ((unsigned)rj >= (unsigned)S) continue;           // no such row: no hits (its slot ran row 0), as k_cfar1d_gated
                 total += wave_append_row(hit + (size_t)j * C, C, total, [&](int pos, int d) {
                     if (pos < a.cap) {
                         out[2 * pos] = rj;

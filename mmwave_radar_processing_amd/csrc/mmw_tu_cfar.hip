@@ -112,6 +112,20 @@ static int cfar1d_args_ok(int kind, int num_train, int num_guard, int k_rank) {
     return MMW_OK;
 }
 
+// k_cfar1d_gated on the listed rows of every frame's plane[F][R][D], then the ordered compaction (arguments judged by the caller)
+static int cfar1d_rows_impl(mmw_ctx *ctx, const double *d_mag64, const int32_t *d_rows, const int32_t *d_nrows, uint8_t *d_mask,
+                            int32_t *d_dets, int32_t *d_counts, int n_frames, int R, int D, int kind, int num_train,
+                            int num_guard, double scale, int k_rank, int cap) {
+    Cfar1dArgs a{d_mag64, nullptr, nullptr, nullptr, 0, D, kind, num_train, num_guard, scale, k_rank};
+    {
+        ProfScope ps(ctx, "cfar");
+        hipLaunchKernelGGL(k_cfar1d_gated, dim3((unsigned)(((long)R * D + 255) / 256), n_frames), dim3(256), 0, ctx->stream, a,
+                           (const int32_t *)nullptr, d_rows, d_nrows, d_mask, R);
+        MMW_TRY(check_launch("cfar1d_rows"));
+    }
+    return compact2d_impl(ctx, d_mask, d_dets, d_counts, n_frames, R, D, cap);
+}
+
 // Every argument of mmw_range_detect is judged here, before the context is touched: the function is not given the context, so a
 // refused call cannot enqueue anything and needs no device (tests/cpp/sar_range_sanitize.cpp relies on it).
 static int range_detect_validate(bool have_ctx, const void *d_cubes, int n_frames, int V, int S, int C, int chirp_idx, int kind,
@@ -273,6 +287,19 @@ int mmw_cfar1d_gated(mmw_ctx *ctx, const double *d_mag64, const int32_t *d_gate,
     return compact2d_impl(ctx, d_mask, d_dets, d_counts, n_frames, R, D, cap);
 }
 
+// mmw_cfar1d_gated with the rows of each frame named by a list (the second half of mmw_seq_detect_plane on a caller's plane)
+int mmw_cfar1d_rows(mmw_ctx *ctx, const double *d_mag64, const int32_t *d_rows, const int32_t *d_nrows, uint8_t *d_mask,
+                    int32_t *d_dets, int32_t *d_counts, int n_frames, int R, int D, int kind, int num_train, int num_guard,
+                    double scale, int k_rank, int cap) {
+    MMW_REQUIRE(ctx && d_mag64 && d_rows && d_nrows && d_mask && d_dets && d_counts, "null argument");
+    MMW_JOIN(ctx);
+    MMW_REQUIRE(n_frames >= 0 && n_frames <= 65535 && R > 0 && D > 0 && cap >= 0, "bad shape");
+    MMW_TRY(cfar1d_args_ok(kind, num_train, num_guard, k_rank));
+    if (n_frames == 0) return MMW_OK;
+    return cfar1d_rows_impl(ctx, d_mag64, d_rows, d_nrows, d_mask, d_dets, d_counts, n_frames, R, D, kind, num_train, num_guard,
+                            scale, k_rank, cap);
+}
+
 // ------------------------------------------------------------------ batched sequential detector (mmw_seq.h)
 int mmw_seq_route(mmw_ctx *ctx, int S, int C) {
     if (opt_int(ctx, "MMW_SEQ_FULL_PLANE", SEQ_FULL_PLANE_DEFAULT) != 0) return 1;
@@ -343,14 +370,8 @@ int mmw_seq_detect_plane(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_row
     MMW_TRY(cfar1d_args_ok(kind, num_train, num_guard, k_rank));
     if (n_frames == 0) return MMW_OK;
     MMW_TRY(range_doppler_mag64_impl(ctx, d_cubes, d_mag64, n_frames, V, S, C, 0));
-    Cfar1dArgs a{d_mag64, nullptr, nullptr, nullptr, 0, C, kind, num_train, num_guard, scale, k_rank};
-    {
-        ProfScope ps(ctx, "cfar");
-        hipLaunchKernelGGL(k_cfar1d_gated, dim3((unsigned)(((long)S * C + 255) / 256), n_frames), dim3(256), 0, ctx->stream, a,
-                           (const int32_t *)nullptr, d_rows, d_nrows, d_mask, S);
-        MMW_TRY(check_launch("cfar1d_rows"));
-    }
-    return compact2d_impl(ctx, d_mask, d_dets, d_counts, n_frames, S, C, cap);
+    return cfar1d_rows_impl(ctx, d_mag64, d_rows, d_nrows, d_mask, d_dets, d_counts, n_frames, S, C, kind, num_train, num_guard,
+                            scale, k_rank, cap);
 }
 
 }  // extern "C"
