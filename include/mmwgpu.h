@@ -695,7 +695,12 @@ int mmw_rd_cells64_at(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_dets, 
  *   d_out [F][S][T] c64.
  *   replaces compute_synthetic_response / compute_response_at_steering_angle
  *   (processors/simple_synthetic_array_beamformer_processor_multiFrame.py:499-585), whose Python loop over steering
- *   angles (:543-585) becomes one complex GEMM per frame.
+ *   angles (:543-585) becomes one complex GEMM per frame.  d_dirs need not be unit vectors; d_t . p / lambda is reduced modulo
+ *   one turn in float64 before anything is narrowed to float32.  MMW_ERR_INVALID, with d_out untouched, for a null ctx, d_X,
+ *   d_P, d_dirs or d_out, n_frames outside 0..65535, S, E or T < 1, and a lambda_m that is not > 0 (NaN included);
+ *   n_frames == 0 returns MMW_OK and writes nothing.  S = 1 gives the bare contraction (np.hanning(1) == [1.]), S = 2 exact
+ *   zeros (that window is all zeros).  A frame whose X or P holds a NaN or an Inf gives non-finite values in that frame's
+ *   S x T outputs only.
  * mmw_capon: MVDR spectrum on a V-element half-wavelength ULA for a batch of frames; NO upstream implementation
  *   exists -- definition in DESIGN.md; d_X [F][V][R][K] c64 (K snapshots per range bin),
  *   d_out [F][R][T] float32.  h_thetas: T angles in radians, host memory, read during the call.  MMW_ERR_INVALID, with
