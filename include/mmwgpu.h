@@ -688,6 +688,32 @@ int mmw_angle_argmax_cells64(mmw_ctx *ctx, const void *d_cells, int32_t *d_idx, 
 int mmw_rd_cells64_at(mmw_ctx *ctx, const void *d_cubes, const int32_t *d_dets, const int32_t *d_counts, void *d_out,
                       int n_frames, int V, int S, int C, int cap, const int *h_ant, int n_ant, int route);
 
+/* TDM-MIMO Doppler phase compensation of the angle estimates.  NO UPSTREAM IMPLEMENTATION: the reference's
+ * PointCloudGenerator._compute_angle_estimation transforms the cells as they are.
+ * h_phase: host [n_ant][C][2] float64, the factor p[i][c] antenna h_ant[i] is multiplied by in fftshifted Doppler column c
+ *   (batch.tdm_phase_table: exp(-2 pi j slot (c - C/2) / (n_slots C))), read during the call.
+ * mmw_angle_argmax_tdm: mmw_angle_argmax_exact of the cells z_i p[i][c]: zero-pad to A, FFT, optional fftshift, |.|,
+ *   first-max argmax (a NaN magnitude wins) -> d_idx[F][cap] int32.  Counts above cap are clamped, frames with a count <= 0
+ *   and the slots from the count on are left as they were, as there.  A float32 pass over d_rd with the worst-case bound of
+ *   mmw_angle_argmax_exact (no pairwise form, no MMW_ARGMAX_BOUND_DIV) widened by the rounding of the float32 phasor and
+ *   product decides what it can; the rest is re-evaluated in float64: complex128 cells of the direct route of
+ *   mmw_rd_cells64_at times the table, angle DFT, argmax.  h_n_refined (may be NULL): their number.  The call synchronises.
+ *   A table whose rows are all the same bit for bit (antennas of one transmit slot) is a common phase: the call IS
+ *   mmw_angle_argmax_exact then.  MMW_ERR_INVALID: what mmw_angle_argmax_exact refuses, a null h_phase, S > 65535.
+ *   MMW_ERR_UNSUPPORTED: (A + distinct rows * C) * 8 bytes beyond 48 KiB of LDS.
+ * mmw_angle_argmax_cells64_tdm: the float64 stage alone for cells the caller gathered: d_cells [n_rows][n_ant] complex128,
+ *   d_cols [n_rows] int32 the Doppler column of each row (clamped to [0, C)), d_idx [n_rows].  Two bins are ordered on
+ *   re^2 + im^2, every operation rounded once (the order of |.| short of overflow).  Synchronises.
+ * mmw_diag_angle_argmax_tdm_host: the same stage in plain C++ on host arrays, bit for bit the device's indices; no device
+ *   is touched (ctx-free). */
+int mmw_angle_argmax_tdm(mmw_ctx *ctx, const void *d_cubes, const float *d_l1, const void *d_rd, const int32_t *d_dets,
+                         const int32_t *d_counts, int32_t *d_idx, int n_frames, int V, int S, int C, int cap,
+                         const int *h_ant, int n_ant, int A, int shift, const double *h_phase, int *h_n_refined);
+int mmw_angle_argmax_cells64_tdm(mmw_ctx *ctx, const void *d_cells, const int32_t *d_cols, const double *h_phase,
+                                 int32_t *d_idx, int n_rows, int n_ant, int C, int A, int shift);
+int mmw_diag_angle_argmax_tdm_host(const void *h_cells, const int32_t *h_cols, const double *h_phase, int32_t *h_idx,
+                                   int n_rows, int n_ant, int C, int A, int shift);
+
 /* ---------------------------------------------------------------- beamformers
  * mmw_bartlett: delay-and-sum steering-matrix contraction on MFMA for a batch of frames,
  *   Y[f][s][t] = FFT_S( hann(S) * sum_e X[f][s][e] hamming(E)[e] exp(j 2 pi d_t . p_{f,e} / lambda) )

@@ -105,6 +105,47 @@ def _check_integrate_rx(integrate_rx, V: int) -> List[int]:
     return ants
 
 
+def tdm_tx_slots_of(tdm_tx_slots, V: int, num_rx: int) -> Tuple[List[int], int]:
+    """The transmit slot of every virtual antenna and the number of slots in a loop, for ``tdm_compensation=True``.  ``None``:
+    ``slot[v] = v // num_rx`` and ``V // num_rx`` slots (the order VirtualArrayReformatter stacks the antennas in).  A list: one
+    non-negative int per virtual antenna; the loop has ``max(slot) + 1`` slots."""
+    if tdm_tx_slots is None:
+        num_rx = int(num_rx)
+        if num_rx < 1 or V % num_rx:
+            raise ValueError(f"tdm_compensation: {V} virtual antennas are no multiple of num_rx_antennas = {num_rx}; pass tdm_tx_slots=")
+        return [v // num_rx for v in range(V)], V // num_rx
+    try:
+        items = list(tdm_tx_slots)
+    except TypeError:
+        raise ValueError(f"tdm_tx_slots= takes a list of ints, got {type(tdm_tx_slots).__name__}") from None
+    if len(items) != V:
+        raise ValueError(f"tdm_tx_slots= needs one slot per virtual antenna ({V}), got {len(items)}")
+    for v in items:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"tdm_tx_slots= takes ints, got {v!r}")
+        if int(v) < 0:
+            raise ValueError(f"tdm_tx_slots=: slot {int(v)} is negative")
+    slots = [int(v) for v in items]
+    return slots, max(slots) + 1
+
+
+def tdm_phase_table(ant, slots, n_slots: int, C: int) -> np.ndarray:
+    """The factors of the TDM-MIMO Doppler phase compensation, complex128 ``[len(ant), C]``:
+    ``p[i][c] = exp(-2 pi j slots[ant[i]] (c - C // 2) / (n_slots C))`` for the fftshifted Doppler column ``c``.  Made once on the
+    host in float64; the kernels, the host twin and the tests' NumPy restatement all multiply by these very values."""
+    ant = np.asarray(ant, dtype=np.int64).reshape(-1)
+    slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+    n_slots, C = int(n_slots), int(C)
+    if n_slots < 1 or C < 1:
+        raise ValueError("tdm_phase_table: n_slots and C must be positive")
+    if ant.size and (ant.min() < -slots.size or ant.max() >= slots.size):
+        raise ValueError("tdm_phase_table: antenna index outside the slot list")
+    k = slots[ant].astype(np.float64)[:, None]
+    col = (np.arange(C, dtype=np.int64) - C // 2).astype(np.float64)[None, :]
+    ang = -2.0 * np.pi * (k * col) / float(n_slots * C)
+    return np.ascontiguousarray(np.cos(ang) + 1j * np.sin(ang), dtype=np.complex128)
+
+
 def _check_sequential(sequential) -> None:
     """What the batched sequential path serves: a RangeDopplerDetectorSequential whose two detectors are stock 1-D CFARs."""
     from .processors.range_doppler_detection.range_doppler_detector_sequential import RangeDopplerDetectorSequential
@@ -350,11 +391,24 @@ class FramePipeline:
     ``integrate_rx=[v0, v1, ...]`` (no upstream counterpart): the 2-D CFAR of ``cfar=`` runs on the float64
     power summed over the listed virtual antennas, ``sum_v |RD_v|^2`` added in list order, in place of antenna 0's ``|RD|``;
     the angle estimates of the detections are unchanged.  Distinct ints in ``[0, V)``; not with ``ground=`` / ``sequential=``.
-    ``integrated_power()`` returns the plane.  ``None`` (the default): the reference's antenna-0 detection."""
+    ``integrated_power()`` returns the plane.  ``None`` (the default): the reference's antenna-0 detection.
+
+    ``tdm_compensation=True`` (no upstream counterpart): the cells of every detection are multiplied by the
+    conjugate of the phase their transmit slot adds at the detection's Doppler bin before the angle FFT
+    (``mmw_angle_argmax_tdm``), in every mode (``cfar=``, ``integrate_rx=``, ``ground=``, ``sequential=``); the detections are
+    those of ``detect()``.  ``tdm_tx_slots``: the slot of each virtual antenna (default ``v // num_rx_antennas``).  ``False``
+    (the default): the reference's angle estimates, nothing added."""
 
     def __init__(self, config_manager, max_frames: int, shape: Tuple[int, int, int], num_angle_bins: int = 64,
                  cfar=None, az_antenna_idxs=(), el_antenna_idxs=(), shift_az_resp=True, shift_el_resp=False,
-                 det_capacity: int = 2048, ctx: _lib.Context = None, ground=None, sequential=None, integrate_rx=None):
+                 det_capacity: int = 2048, ctx: _lib.Context = None, ground=None, sequential=None, integrate_rx=None,
+                 tdm_compensation: bool = False, tdm_tx_slots=None):
+        self.tdm_compensation = bool(tdm_compensation)
+        self.tdm_slots = None
+        if self.tdm_compensation:
+            self.tdm_slots = tdm_tx_slots_of(tdm_tx_slots, int(shape[0]), getattr(config_manager, "num_rx_antennas", 0))
+        elif tdm_tx_slots is not None:
+            tdm_tx_slots_of(tdm_tx_slots, int(shape[0]), 1)      # (a bad list is refused whether or not it is used)
         self.integrate_rx = None
         if integrate_rx is not None:
             if ground is not None or sequential is not None:
@@ -1446,6 +1500,14 @@ class FramePipeline:
         cap = self.cap
         arr, n_ant = _lib.int_array(ant)
         n_ref = _lib.C.c_int(0)
+        if self.tdm_compensation:
+            table = tdm_phase_table(ant, self.tdm_slots[0], self.tdm_slots[1], self.C)
+            _lib.check(self.ctx.lib.mmw_angle_argmax_tdm(self.ctx.handle, self.d_in.at(f0 * self.cube_bytes), self.d_l1.at(f0 * self.V * 4),
+                                                         self.d_rd.at(f0 * self.cube_bytes), self.d_dets.at(f0 * cap * 8),
+                                                         self.d_cnt.at(f0 * 4), d_idx.at(f0 * cap * 4), nf, self.V, self.S, self.C,
+                                                         cap, arr, n_ant, self.A, int(shift), table.ctypes.data, _lib.C.byref(n_ref)))
+            self.n_refined += n_ref.value
+            return
         _lib.check(self.ctx.lib.mmw_angle_argmax_exact(self.ctx.handle, self.d_in.at(f0 * self.cube_bytes), self.d_l1.at(f0 * self.V * 4),
                                                        self.d_rd.at(f0 * self.cube_bytes), self.d_dets.at(f0 * cap * 8),
                                                        self.d_cnt.at(f0 * 4), d_idx.at(f0 * cap * 4), nf, self.V, self.S, self.C,
@@ -1642,7 +1704,8 @@ class FramePipeline:
         return self.d_cnt.download((F,), np.int32)
 
     def _argmax_device(self, ant, shift, name) -> _lib.DeviceBuffer:
-        """Exact (float64-equivalent) argmax bins of every detection, ``[F, cap]`` int32 on the device: ``mmw_angle_argmax_exact``."""
+        """Exact (float64-equivalent) argmax bins of every detection, ``[F, cap]`` int32 on the device: ``mmw_angle_argmax_exact``
+        (``tdm_compensation=True``: ``mmw_angle_argmax_tdm``)."""
         F, cap = self.n_frames, self.cap
         d_idx = self.bufs.get(name, max(F, 1) * cap * 4)
         for f0 in range(0, F, 32768):
@@ -1654,7 +1717,8 @@ class FramePipeline:
         empty antenna list leaves None).  ``fetch``: also the host lists of ``detect()`` (``self.dets``).  Returns the counts."""
         self.n_refined = 0      # detections re-evaluated in float64 (near-ties of the float32 pass)
         self._alloc_detect()
-        if self.ground is None and self.sequential is None and self.integrate_rx is None and self._fused_supported(True):
+        if (self.ground is None and self.sequential is None and self.integrate_rx is None and not self.tdm_compensation
+                and self._fused_supported(True)):
             counts = self._detect_fused(True)
             self._fetch_dets(counts) if fetch else self._check_capacity(counts)
             return counts

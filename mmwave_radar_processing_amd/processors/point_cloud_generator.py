@@ -31,7 +31,15 @@ class PointCloudGenerator(_Processor):
     def __init__(self, config_manager, az_antenna_idxs: Union[List[int], np.ndarray],
                  el_antenna_idxs: Union[List[int], np.ndarray], detector_type: str = "range_doppler_detector_2d",
                  detector_params: Dict = {}, shift_az_resp: bool = True, shift_el_resp: bool = False,
-                 num_angle_bins: int = 64, **kwargs):
+                 num_angle_bins: int = 64, tdm_compensation: bool = False, tdm_tx_slots=None, **kwargs):
+        # TDM-MIMO Doppler phase compensation of the angle estimates (no upstream counterpart); off: the reference
+        self.tdm_compensation = bool(tdm_compensation)
+        self.tdm_slots = None
+        if self.tdm_compensation or tdm_tx_slots is not None:
+            from ..batch import tdm_tx_slots_of
+            num_rx = int(getattr(config_manager, "num_rx_antennas", 0))
+            slots = tdm_tx_slots_of(tdm_tx_slots, num_rx * int(getattr(config_manager, "num_tx_antennas", 0)), num_rx)
+            self.tdm_slots = slots if self.tdm_compensation else None
         self.shift_az_resp = shift_az_resp
         self.shift_el_resp = shift_el_resp
         self.az_antenna_idxs = _as_index_array(az_antenna_idxs, "az_antenna_idxs")
@@ -56,7 +64,7 @@ class PointCloudGenerator(_Processor):
         # detections and both argmax index lists from ONE device call where the detector has the fused kernel
         # (RangeDopplerDetector2D with a CA-CFAR whose plane fits the LDS, lists of <= 8 antennas): mmw_detect_points
         fused = getattr(det, "process_points", None)
-        if fused is not None and max(self.az_antenna_idxs.size, self.el_antenna_idxs.size) <= 8:
+        if fused is not None and not self.tdm_compensation and max(self.az_antenna_idxs.size, self.el_antenna_idxs.size) <= 8:
             dets = fused(adc_cube, [int(i) for i in self.az_antenna_idxs], [int(i) for i in self.el_antenna_idxs],
                          self.shift_az_resp, self.shift_el_resp, self.num_angle_bins)
             if dets is not None:
@@ -119,7 +127,17 @@ class PointCloudGenerator(_Processor):
             if ant.size == 0:
                 out.append(np.zeros(n))
                 continue
-            if resident:
+            table = None
+            if self.tdm_compensation:
+                from ..batch import tdm_phase_table
+                table = tdm_phase_table(ant, self.tdm_slots[0], self.tdm_slots[1], C if resident else raw.shape[2])
+            if resident and table is not None:
+                arr, n_ant = _lib.int_array(ant)
+                n_ref = _lib.C.c_int(0)
+                _lib.check(L.mmw_angle_argmax_tdm(h, d_cube.ptr, d_l1.ptr, d_rd.ptr, d_dets.ptr, d_cnt.ptr, d_idx.ptr, 1, V, S, C, n,
+                                                  arr, n_ant, A, int(bool(shift)), table.ctypes.data, _lib.C.byref(n_ref)))
+                self.n_refined += n_ref.value
+            elif resident:
                 arr, n_ant = _lib.int_array(ant)
                 n_ref = _lib.C.c_int(0)
                 _lib.check(L.mmw_angle_argmax_exact(h, d_cube.ptr, d_l1.ptr, d_rd.ptr, d_dets.ptr, d_cnt.ptr, d_idx.ptr, 1,
@@ -129,6 +147,13 @@ class PointCloudGenerator(_Processor):
                 cells = np.ascontiguousarray(raw[ant][:, r_idx, v_idx].T, dtype=np.complex128)     # (N, n_ant), :168-175
                 d_cells = bufs.get("pc_cells", cells.nbytes)
                 d_cells.upload(cells)
+                if table is not None:
+                    d_cols = bufs.get("pc_cols", n * 4)
+                    d_cols.upload(np.ascontiguousarray(v_idx, dtype=np.int32))
+                    _lib.check(L.mmw_angle_argmax_cells64_tdm(h, d_cells.ptr, d_cols.ptr, table.ctypes.data, d_idx.ptr, n, cells.shape[1],
+                                                              raw.shape[2], A, int(bool(shift))))
+                    out.append(self.angle_bins[d_idx.download((n,), np.int32).astype(int)])
+                    continue
                 _lib.check(L.mmw_angle_argmax_cells64(h, d_cells.ptr, d_idx.ptr, n, cells.shape[1], A, int(bool(shift))))
             out.append(self.angle_bins[d_idx.download((n,), np.int32).astype(int)])
         return out[0], out[1]

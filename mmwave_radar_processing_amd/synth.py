@@ -78,6 +78,35 @@ def synth_raw_cube(seed: int, num_rx: int = 4, num_tx: int = 3, num_samples: int
     return raw
 
 
+def synth_tdm_targets(seed: int, num_rx: int, num_tx: int, S: int, loops: int, targets, noise_sigma: float = 0.0,
+                      num_angle_bins: int = 64, shift: bool = True):
+    """Raw TDM-MIMO cube ``[num_rx, S, num_tx * loops]`` complex64 of point targets, and each target's true angle bin.
+
+    ``targets``: rows ``(amplitude, f_range, f_doppler, f_spatial)`` -- cycles per sample, cycles per RAW chirp and cycles per
+    virtual element.  Raw chirp ``n = loop * num_tx + tx`` is sent by transmitter ``tx``; receiver ``rx`` then is element
+    ``tx * num_rx + rx`` of a uniform virtual array (the order VirtualArrayReformatter stacks).  The Doppler phase runs over the raw
+    chirp index, so the antennas of transmit slot ``tx`` carry ``2 pi f_doppler tx`` from the chirp timing itself: nothing is
+    injected.  A target on Doppler bin ``kd`` of the de-interleaved cube has ``f_doppler = kd / (num_tx * loops)``.
+    ``noise_sigma``: complex Gaussian noise from ``default_rng(seed)``; the samples are NOT rounded to integers.
+    The true bin of a target is ``round(f_spatial * num_angle_bins)`` modulo the FFT size, fftshifted with ``shift``."""
+    t = np.asarray(targets, dtype=np.float64).reshape(-1, 4)
+    rng = np.random.default_rng(seed)
+    rx = np.arange(num_rx)[:, None, None]
+    s = np.arange(S)[None, :, None]
+    n = np.arange(num_tx * loops)[None, None, :]
+    elem = (n % num_tx) * num_rx + rx
+    x = np.zeros((num_rx, S, num_tx * loops), dtype=np.complex128)
+    for amp, f_r, f_d, f_a in t:
+        x += amp * np.exp(2j * np.pi * (f_r * s + f_d * n + f_a * elem))
+    if noise_sigma:
+        x += noise_sigma * (rng.standard_normal(x.shape) + 1j * rng.standard_normal(x.shape))
+    A = int(num_angle_bins)
+    bins = np.rint(t[:, 3] * A).astype(np.int64) % A
+    if shift:
+        bins = (bins + A // 2) % A
+    return x.astype(np.complex64), bins
+
+
 def synth_ground_sequence(seed: int, n_frames: int = 5, shape=(12, 256, 128), range_res_m: float = 0.0975887,
                           altitude0_m: float = 1.02, climb_m: float = 0.07, ground_amp: float = 350.0,
                           num_clutter: int = 3, noise_sigma: float = 30.0) -> np.ndarray:
