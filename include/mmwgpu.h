@@ -185,6 +185,12 @@ int mmw_dbs_sharpen(mmw_ctx *ctx, const void *d_cubes, void *d_rd, const int32_t
  *   the rows of the range window, np.max over them.  Only antenna rx_idx's [S][C] slab of a frame is read, only the rows of the
  *   window are computed (a partial DFT over fast time, direct DFTs over slow time, float32), and nothing but the C floats of a
  *   frame is written.  Any S, C >= 1 up to 3444 chirps (MMW_ERR_UNSUPPORTED beyond: the rows in flight live in the LDS).
+ *   Range: the magnitude is sqrt(re^2 + im^2) in float32, not hypot.  Scaling a slab by 2^e scales its row by 2^e bit for bit, and
+ *   every value lies within ulps(S, C) 2^-24 of L1 = sum |x[s][c]| from the exact one (tests/partial_dft_cases.py counts ulps),
+ *   for as long as every partial sum, im^2 and re^2 + im^2 of the frame are normal, finite float32 numbers; L1 < 2^63 keeps them
+ *   finite, and an output below 2^-63 may have lost its precision or be 0.  A NaN anywhere in the slab (either sign) makes the
+ *   frame's whole row NaN, an infinity leaves no finite value in it, an all-zero slab gives +0.0; other frames and the other
+ *   antennas are not touched by either.
  *   MMW_ERR_INVALID (nothing launched, d_out untouched): a null pointer, n_frames < 0, rx_idx outside [0, V), row_lo > row_hi,
  *   a row outside [0, S).  n_frames == 0: MMW_OK, nothing launched.  Profile family "micro_doppler". */
 int mmw_micro_doppler(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_frames, int V, int S, int C, int rx_idx, int row_lo,
@@ -202,6 +208,10 @@ int mmw_micro_doppler(mmw_ctx *ctx, const void *d_cubes, float *d_out, int n_fra
  *   mmw_micro_doppler serves (MMW_ERR_UNSUPPORTED beyond: the rows in flight live in the LDS; the shape is judged before the
  *   windows, so also when every window is empty, where a served shape returns MMW_OK with nothing launched).  The grid is capped at 4096
  *   workgroups; with more frames a workgroup walks frames f, f + 4096, ...
+ *   Range: the blocks are complex and nothing is squared, so the same bound (every element within ulps(S, C) 2^-24 L1 of the exact
+ *   one) and the bit-for-bit scaling by 2^e hold on the wider interval on which every partial sum is a normal, finite float32
+ *   number; L1 < 2^127 keeps them finite.  A NaN in the slab makes every element of the frame's block NaN, an infinity leaves
+ *   none finite, an all-zero slab gives +0.0 in both parts; other frames are not touched.
  *   MMW_ERR_INVALID (nothing launched, d_out untouched): a null pointer, n_frames < 0, rx_idx outside [0, V), a window reversed
  *   or outside [0, S] x [0, C], h_off[0] != 0, h_off[f + 1] - h_off[f] different from the window's area.  n_frames == 0: MMW_OK,
  *   nothing launched.  Profile family "sar_slices". */
