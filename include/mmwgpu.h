@@ -724,6 +724,46 @@ int mmw_angle_argmax_cells64_tdm(mmw_ctx *ctx, const void *d_cells, const int32_
 int mmw_diag_angle_argmax_tdm_host(const void *h_cells, const int32_t *h_cols, const double *h_phase, int32_t *h_idx,
                                    int n_rows, int n_ant, int C, int A, int shift);
 
+/* TDM-MIMO velocity unwrapping: Doppler hypotheses per detection.  NO UPSTREAM IMPLEMENTATION.
+ * A target's Doppler bin is known modulo C: its true bin is k + h C (k = c - C/2) for one h in [0, n_slots), and the
+ * compensation above needs the factor of that bin.  h_phase: host [H][n_ant][C][2] float64, one table per hypothesis
+ *   (batch.tdm_hypothesis_table: exp(-2 pi j sym(slot (k + h C)) / (n_slots C)), the phase reduced as an integer), read during
+ *   the call; 1 <= H <= 8.  A hypothesis whose [n_ant][C] block equals an earlier one's bit for bit, or is, like an earlier
+ *   one, a phase common to the whole list (all rows equal bit for bit), is a DUPLICATE: it is never evaluated and stands for
+ *   the earlier one.
+ * mmw_angle_argmax_tdm_hyp: for every live detection, P_h = max over the A bins of re^2 + im^2 of the DFT of z_i p_h[i][c]
+ *   for each distinct h in ascending order; h* = the first maximum over h (a NaN wins); the angle index = the first-maximum
+ *   bin of h*, fftshifted with shift.  hyp_given == 0: d_hyp[F][cap] int32 <- h* (its original number), d_idx <- the index.
+ *   hyp_given != 0: d_hyp is READ: only hypothesis d_hyp[slot] (clamped to [0, H), a duplicate mapped to the one it
+ *   duplicates) is evaluated, d_idx <- its index, d_hyp is left alone.  Counts above cap, frames with a count <= 0 and the
+ *   slots from the count on: as mmw_angle_argmax_tdm.  A float32 pass (one lane per detection, every distinct hypothesis in
+ *   turn) decides what the rule of mmw_angle_argmax_tdm lets it decide ACROSS all (h, bin) pairs; the rest -- NaN / inf
+ *   magnitudes, A == 1 and exact ties between hypotheses included -- is re-evaluated in float64 by that entry's route.
+ *   h_n_refined (may be NULL): their number.  The call synchronises.  With one distinct hypothesis the call IS
+ *   mmw_angle_argmax_tdm on table 0, and (hyp_given == 0) the live slots of d_hyp are set to 0.
+ *   MMW_ERR_INVALID: what mmw_angle_argmax_tdm refuses, a null d_hyp, H < 1, H > 8.
+ *   MMW_ERR_UNSUPPORTED: (A + distinct float32 phasor rows * C) * 8 bytes beyond 48 KiB of LDS.
+ * mmw_angle_argmax_cells64_tdm_hyp: the float64 stage alone for cells the caller gathered (d_cells [n_rows][n_ant]
+ *   complex128, d_cols [n_rows] int32, d_idx / d_hyp [n_rows]).  Synchronises.
+ * mmw_diag_angle_argmax_tdm_hyp_host: the same stage in plain C++ on host arrays, bit for bit the device's d_idx and d_hyp;
+ *   no device is touched (ctx-free).
+ * mmw_tdm_unwrap_velocity: for every live slot of d_points [F][cap][4] float64 (mmw_point_cloud), with c the detection's
+ *   Doppler column (outside [0, C): 0, as there), k = c - C/2, M = n_slots C, sym(q) = ((q + M/2) mod M) - M/2 (floor mod),
+ *   h = d_hyp[slot] clamped to [0, n_slots): k' = sym(k + h C), m = (k' - k) / C; where m != 0, column 3 <- column 3 +
+ *   float64(m) * span (one multiply, one add); where m == 0 the slot is not written.  1 <= n_slots <= 8.  Asynchronous. */
+int mmw_angle_argmax_tdm_hyp(mmw_ctx *ctx, const void *d_cubes, const float *d_l1, const void *d_rd, const int32_t *d_dets,
+                             const int32_t *d_counts, int32_t *d_idx, int32_t *d_hyp, int hyp_given, int n_frames, int V,
+                             int S, int C, int cap, const int *h_ant, int n_ant, int A, int shift, const double *h_phase,
+                             int H, int *h_n_refined);
+int mmw_angle_argmax_cells64_tdm_hyp(mmw_ctx *ctx, const void *d_cells, const int32_t *d_cols, const double *h_phase, int H,
+                                     int32_t *d_idx, int32_t *d_hyp, int hyp_given, int n_rows, int n_ant, int C, int A,
+                                     int shift);
+int mmw_diag_angle_argmax_tdm_hyp_host(const void *h_cells, const int32_t *h_cols, const double *h_phase, int H,
+                                       int32_t *h_idx, int32_t *h_hyp, int hyp_given, int n_rows, int n_ant, int C, int A,
+                                       int shift);
+int mmw_tdm_unwrap_velocity(mmw_ctx *ctx, double *d_points, const int32_t *d_dets, const int32_t *d_counts,
+                            const int32_t *d_hyp, int n_frames, int cap, int C, int n_slots, double span);
+
 /* ---------------------------------------------------------------- beamformers
  * mmw_bartlett: delay-and-sum steering-matrix contraction on MFMA for a batch of frames,
  *   Y[f][s][t] = FFT_S( hann(S) * sum_e X[f][s][e] hamming(E)[e] exp(j 2 pi d_t . p_{f,e} / lambda) )

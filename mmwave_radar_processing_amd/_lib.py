@@ -140,6 +140,10 @@ _SIGNATURES = {
     "mmw_angle_argmax_tdm": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _i, _i, _vp, _ip],
     "mmw_angle_argmax_cells64_tdm": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i],
     "mmw_diag_angle_argmax_tdm_host": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i],
+    "mmw_angle_argmax_tdm_hyp": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _ip, _i, _i, _i, _vp, _i, _ip],
+    "mmw_angle_argmax_cells64_tdm_hyp": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i],
+    "mmw_diag_angle_argmax_tdm_hyp_host": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i],
+    "mmw_tdm_unwrap_velocity": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d],
     "mmw_bartlett": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d],
     "mmw_capon": [_vp, _vp, C.POINTER(_d), _vp, _i, _i, _i, _i, _i, _d],
     "mmw_range_snapshots": [_vp, _vp, _vp, _i, _i, _i, _i, _ip, _i, _i, _i, _i],

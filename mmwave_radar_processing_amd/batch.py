@@ -146,6 +146,87 @@ def tdm_phase_table(ant, slots, n_slots: int, C: int) -> np.ndarray:
     return np.ascontiguousarray(np.cos(ang) + 1j * np.sin(ang), dtype=np.complex128)
 
 
+def tdm_unwrapped_bin(c, h, n_slots: int, C: int):
+    """The Doppler bin of fftshifted column ``c`` under velocity hypothesis ``h``: ``k' = sym(k + h C)`` with
+    ``k = c - C // 2``, ``M = n_slots C`` and ``sym(q) = ((q + M // 2) mod M) - M // 2`` (integers, floor mod).  Scalars or arrays;
+    ``m = (k' - k) / C`` is exact, and ``|m| <= (n_slots + 1) // 2``."""
+    n_slots, C = int(n_slots), int(C)
+    if n_slots < 1 or C < 1:
+        raise ValueError("tdm_unwrapped_bin: n_slots and C must be positive")
+    M = n_slots * C
+    q = (np.asarray(c, dtype=np.int64) - C // 2) + np.asarray(h, dtype=np.int64) * C
+    out = ((q + M // 2) % M) - M // 2
+    return int(out) if out.ndim == 0 else out
+
+
+def tdm_hypothesis_table(ant, slots, n_slots: int, C: int) -> np.ndarray:
+    """The factors of every velocity hypothesis of a TDM-MIMO detection, complex128 ``[n_slots, len(ant), C]``:
+    ``p_h[i][c] = exp(-2 pi j q / M)`` with ``q = sym(slots[ant[i]] (k + h C))``, ``k = c - C // 2``, ``M = n_slots C`` -- the phase
+    is reduced as an int64 before it becomes a float, so hypotheses the list cannot tell apart are equal bit for bit, and
+    ``table[0]`` is ``tdm_phase_table(ant, slots, n_slots, C)`` bit for bit (``|slot k| < M / 2``: the reduction leaves it alone)."""
+    ant = np.asarray(ant, dtype=np.int64).reshape(-1)
+    slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+    n_slots, C = int(n_slots), int(C)
+    if n_slots < 1 or C < 1:
+        raise ValueError("tdm_hypothesis_table: n_slots and C must be positive")
+    if ant.size and (ant.min() < -slots.size or ant.max() >= slots.size):
+        raise ValueError("tdm_hypothesis_table: antenna index outside the slot list")
+    M = n_slots * C
+    k = (np.arange(C, dtype=np.int64) - C // 2)[None, None, :]
+    h = np.arange(n_slots, dtype=np.int64)[:, None, None]
+    q = slots[ant][None, :, None] * (k + h * C)
+    q = ((q + M // 2) % M) - M // 2
+    ang = -2.0 * np.pi * q.astype(np.float64) / float(M)
+    return np.ascontiguousarray(np.cos(ang) + 1j * np.sin(ang), dtype=np.complex128)
+
+
+def tdm_hypothesis_list_of(tdm_hypothesis_list, az, el, tdm_slots) -> Tuple[str, List[int]]:
+    """The list whose angle peak decides the velocity hypothesis, for ``tdm_velocity_unwrap=True``: ``("az" | "el" | "list",
+    antennas)``.  ``"az"`` / ``"el"``: the pipeline's own list; else distinct ints.  A list inside one transmit slot is refused (its
+    hypotheses differ by a common phase: it carries no information), and so are more than 8 slots.  Whether the list is a
+    UNIFORM aperture -- which the decision needs -- cannot be checked here."""
+    slots, n_slots = tdm_slots
+    if isinstance(tdm_hypothesis_list, str):
+        if tdm_hypothesis_list not in ("az", "el"):
+            raise ValueError(f"tdm_hypothesis_list= takes 'az', 'el' or a list of antennas, got {tdm_hypothesis_list!r}")
+        which, ants = tdm_hypothesis_list, list(az if tdm_hypothesis_list == "az" else el)
+    else:
+        try:
+            items = list(tdm_hypothesis_list)
+        except TypeError:
+            raise ValueError(f"tdm_hypothesis_list= takes 'az', 'el' or a list of antennas, got "
+                             f"{type(tdm_hypothesis_list).__name__}") from None
+        for v in items:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -len(slots) <= int(v) < len(slots):
+                raise ValueError(f"tdm_hypothesis_list=: {v!r} is no antenna index of {len(slots)} virtual antennas")
+        which, ants = "list", [int(v) for v in items]
+        if len(set(a % len(slots) for a in ants)) != len(ants) or len(ants) > 32:
+            raise ValueError(f"tdm_hypothesis_list=: up to 32 distinct antennas, got {ants}")
+    if n_slots > 8:
+        raise ValueError(f"tdm_velocity_unwrap: {n_slots} transmit slots, at most 8 hypotheses are evaluated")
+    if len(set(slots[a] for a in ants)) < 2:
+        raise ValueError(f"tdm_velocity_unwrap: the deciding list {ants} lies inside one transmit slot and carries no information "
+                         "about the velocity hypothesis; pass tdm_hypothesis_list=")
+    return which, ants
+
+
+def tdm_distinct_hypotheses(table: np.ndarray) -> List[int]:
+    """For every hypothesis of a ``[H, n_ant, C]`` table the number of the hypothesis that stands for it: itself,
+    or the first earlier one whose block is equal bit for bit or is, like its own, a phase common to the whole list (all rows
+    equal bit for bit -- no magnitude can tell two of those apart).  The rule the library applies with ``memcmp``."""
+    t = np.ascontiguousarray(table, dtype=np.complex128)
+    common = [all(t[h, i].tobytes() == t[h, 0].tobytes() for i in range(t.shape[1])) for h in range(t.shape[0])]
+    out: List[int] = []
+    for h in range(t.shape[0]):
+        rep = h
+        for g in range(h):
+            if out[g] == g and ((common[h] and common[g]) or t[h].tobytes() == t[g].tobytes()):
+                rep = g
+                break
+        out.append(rep)
+    return out
+
+
 def _check_sequential(sequential) -> None:
     """What the batched sequential path serves: a RangeDopplerDetectorSequential whose two detectors are stock 1-D CFARs."""
     from .processors.range_doppler_detection.range_doppler_detector_sequential import RangeDopplerDetectorSequential
@@ -397,13 +478,24 @@ class FramePipeline:
     conjugate of the phase their transmit slot adds at the detection's Doppler bin before the angle FFT
     (``mmw_angle_argmax_tdm``), in every mode (``cfar=``, ``integrate_rx=``, ``ground=``, ``sequential=``); the detections are
     those of ``detect()``.  ``tdm_tx_slots``: the slot of each virtual antenna (default ``v // num_rx_antennas``).  ``False``
-    (the default): the reference's angle estimates, nothing added."""
+    (the default): the reference's angle estimates, nothing added.
+
+    ``tdm_velocity_unwrap=True`` (with ``tdm_compensation=True``; no upstream counterpart): a target faster than the
+    TDM-reduced ``vel_max`` folds back into the plane and would be compensated with the wrong factor.  Each detection is evaluated
+    under its ``n_slots`` Doppler hypotheses ``k + h C`` on the deciding list (``tdm_hypothesis_list``: ``"az"``, ``"el"`` or an
+    antenna list that spans at least two slots -- it must be a UNIFORM aperture, which is not checked) and the hypothesis with the
+    highest angle peak is kept (``mmw_angle_argmax_tdm_hyp``); the other list is compensated with that hypothesis, and the ``v``
+    column becomes ``vel_bins[c] + m * 2 vel_max`` (``mmw_tdm_unwrap_velocity``).  ``tdm_hypotheses()`` / ``tdm_unwrapped_bins()``
+    return the choices.  ``False`` (the default): nothing added to any path."""
 
     def __init__(self, config_manager, max_frames: int, shape: Tuple[int, int, int], num_angle_bins: int = 64,
                  cfar=None, az_antenna_idxs=(), el_antenna_idxs=(), shift_az_resp=True, shift_el_resp=False,
                  det_capacity: int = 2048, ctx: _lib.Context = None, ground=None, sequential=None, integrate_rx=None,
-                 tdm_compensation: bool = False, tdm_tx_slots=None):
+                 tdm_compensation: bool = False, tdm_tx_slots=None, tdm_velocity_unwrap: bool = False, tdm_hypothesis_list="az"):
         self.tdm_compensation = bool(tdm_compensation)
+        self.tdm_velocity_unwrap = bool(tdm_velocity_unwrap)
+        if self.tdm_velocity_unwrap and not self.tdm_compensation:
+            raise ValueError("FramePipeline: tdm_velocity_unwrap=True chooses among the factors of tdm_compensation=True; pass both")
         self.tdm_slots = None
         if self.tdm_compensation:
             self.tdm_slots = tdm_tx_slots_of(tdm_tx_slots, int(shape[0]), getattr(config_manager, "num_rx_antennas", 0))
@@ -436,6 +528,9 @@ class FramePipeline:
         self.az = [int(i) for i in az_antenna_idxs]
         self.el = [int(i) for i in el_antenna_idxs]
         self.shift_az, self.shift_el = bool(shift_az_resp), bool(shift_el_resp)
+        self.tdm_hyp_list = None
+        if self.tdm_velocity_unwrap:
+            self.tdm_hyp_list = tdm_hypothesis_list_of(tdm_hypothesis_list, self.az, self.el, self.tdm_slots)
         self.cap = int(det_capacity)
         self.ctx = ctx if ctx is not None else _lib.default_context()
         self.bufs = _lib.BufferSet(self.ctx)
@@ -1514,6 +1609,60 @@ class FramePipeline:
                                                        cap, arr, n_ant, self.A, int(shift), _lib.C.byref(n_ref)))
         self.n_refined += n_ref.value
 
+    def _argmax_hypotheses(self):
+        """``tdm_velocity_unwrap=True``: the deciding list through ``mmw_angle_argmax_tdm_hyp`` (every hypothesis; ``d_hyp`` gets the
+        choice), the other list(s) through the same entry with the hypothesis given."""
+        F, cap = self.n_frames, self.cap
+        which, deciding = self.tdm_hyp_list
+        slots, n_slots = self.tdm_slots
+        self.d_hyp = self.bufs.get("tdm_hyp", max(F, 1) * cap * 4)
+        lists = {"az": (self.az, self.shift_az, "az_idx"), "el": (self.el, self.shift_el, "el_idx"),
+                 "list": (deciding, False, "tdm_hyp_idx")}
+        out = {}
+        for key in (which,) + tuple(k for k in ("az", "el") if k != which):
+            ant, shift, name = lists[key]
+            if not ant:
+                out[key] = None
+                continue
+            d_idx = out[key] = self.bufs.get(name, max(F, 1) * cap * 4)
+            arr, n_ant = _lib.int_array(ant)
+            table = tdm_hypothesis_table(ant, slots, n_slots, self.C)
+            for f0 in range(0, F, 32768):
+                n_ref = _lib.C.c_int(0)
+                _lib.check(self.ctx.lib.mmw_angle_argmax_tdm_hyp(
+                    self.ctx.handle, self.d_in.at(f0 * self.cube_bytes), self.d_l1.at(f0 * self.V * 4), self.d_rd.at(f0 * self.cube_bytes),
+                    self.d_dets.at(f0 * cap * 8), self.d_cnt.at(f0 * 4), d_idx.at(f0 * cap * 4), self.d_hyp.at(f0 * cap * 4),
+                    int(key != which), min(32768, F - f0), self.V, self.S, self.C, cap, arr, n_ant, self.A, int(shift),
+                    table.ctypes.data, n_slots, _lib.C.byref(n_ref)))
+                self.n_refined += n_ref.value
+        self.d_az, self.d_el = out["az"], out["el"]
+
+    def _tdm_hyp_host(self) -> np.ndarray:
+        """``d_hyp`` on the host, ``[F, cap]`` int32, the slots past a frame's count zeroed."""
+        if not self.tdm_velocity_unwrap or self.__dict__.get("d_hyp") is None:
+            raise ValueError("tdm_hypotheses: needs tdm_velocity_unwrap=True and a point-cloud call on the resident frames")
+        hyp = self.d_hyp.download((self.n_frames, self.cap), np.int32).copy()
+        hyp[np.arange(self.cap)[None, :] >= np.clip(self.counts, 0, self.cap)[:, None]] = 0
+        return hyp
+
+    def tdm_hypotheses(self, lo: int = 0, hi: Optional[int] = None) -> np.ndarray:
+        """The velocity hypothesis ``h*`` of every detection of frames ``[lo, hi)`` after a point-cloud call with
+        ``tdm_velocity_unwrap=True``: int32 ``[hi - lo, cap]``, frame f's ``counts[f]`` detections first, zeros behind them."""
+        hyp = self._tdm_hyp_host()
+        lo, hi, _ = slice(lo, hi).indices(self.n_frames)
+        return hyp[lo:max(hi, lo)]
+
+    def tdm_unwrapped_bins(self, lo: int = 0, hi: Optional[int] = None) -> np.ndarray:
+        """The unwrapped Doppler bins ``k' = sym(k + h* C)`` of the same detections (``tdm_unwrapped_bin``): int64 ``[hi - lo, cap]``,
+        zeros behind a frame's detections."""
+        hyp = self._tdm_hyp_host()
+        lo, hi, _ = slice(lo, hi).indices(self.n_frames)
+        hi = max(hi, lo)
+        cols = self.d_dets.download((self.n_frames, self.cap, 2), np.int32)[lo:hi, :, 1]
+        out = tdm_unwrapped_bin(cols, hyp[lo:hi], self.tdm_slots[1], self.C)
+        out[np.arange(self.cap)[None, :] >= np.clip(self.counts[lo:hi], 0, self.cap)[:, None]] = 0
+        return out
+
     def _fused_supported(self, with_angles: bool) -> bool:
         kind, tr, td, gr, gd, _, _ = self._cfar_args()
         n_az, n_el = (len(self.az), len(self.el)) if with_angles else (0, 0)
@@ -1724,6 +1873,9 @@ class FramePipeline:
             return counts
         counts = self._detect_sequential(True) if self.sequential is not None else self._detect_counts()
         self._fetch_dets(counts) if fetch else self._check_capacity(counts)
+        if self.tdm_velocity_unwrap:
+            self._argmax_hypotheses()
+            return counts
         self.d_az = self._argmax_device(self.az, self.shift_az, "az_idx") if self.az else None
         self.d_el = self._argmax_device(self.el, self.shift_el, "el_idx") if self.el else None
         return counts
@@ -1735,6 +1887,8 @@ class FramePipeline:
         dets = self.dets
         az_idx = self.d_az.download((F, cap), np.int32) if self.az else None
         el_idx = self.d_el.download((F, cap), np.int32) if self.el else None
+        if self.tdm_velocity_unwrap:
+            hyp, span = self.d_hyp.download((F, cap), np.int32), 2.0 * self.cm.vel_max_m_s
         out = []
         for f, d in enumerate(dets):
             n = d.shape[0]
@@ -1744,6 +1898,10 @@ class FramePipeline:
             az = self.angle_bins[az_idx[f, :n]] if az_idx is not None else np.zeros(n)
             el = self.angle_bins[el_idx[f, :n]] if el_idx is not None else np.zeros(n)
             rng, vel = self.range_bins[d[:, 0]], self.vel_bins[d[:, 1]]
+            if self.tdm_velocity_unwrap:        # v + m span where the chosen hypothesis folds; m == 0 keeps the table's bits
+                k = d[:, 1] - self.C // 2
+                m = (tdm_unwrapped_bin(d[:, 1], hyp[f, :n], self.tdm_slots[1], self.C) - k) // self.C
+                vel = np.where(m != 0, vel + m.astype(np.float64) * span, vel)
             cos_el = np.cos(el)
             out.append(np.column_stack((rng * cos_el * np.cos(az), rng * cos_el * np.sin(az), rng * np.sin(el), vel)))
         self.az_idx = None if az_idx is None else [az_idx[f, :len(d)].astype(np.int64) for f, d in enumerate(dets)]
@@ -1771,6 +1929,11 @@ class FramePipeline:
                 self.ctx.handle, self.d_dets.at(f0 * cap * 8), self.d_cnt.at(f0 * 4), d_az.at(f0 * cap * 4) if d_az else None,
                 d_el.at(f0 * cap * 4) if d_el else None, tabs[0].ptr, tabs[1].ptr, tabs[2].ptr, tabs[3].ptr,
                 self.d_points.at(f0 * cap * 32), min(32768, F - f0), cap, len(self.range_bins), len(self.vel_bins), self.A))
+            if self.tdm_velocity_unwrap:
+                _lib.check(self.ctx.lib.mmw_tdm_unwrap_velocity(
+                    self.ctx.handle, self.d_points.at(f0 * cap * 32), self.d_dets.at(f0 * cap * 8), self.d_cnt.at(f0 * 4),
+                    self.d_hyp.at(f0 * cap * 4), min(32768, F - f0), cap, self.C, self.tdm_slots[1],
+                    2.0 * self.cm.vel_max_m_s))
         self._points_cnt = self.d_cnt
         return self.d_points
 

@@ -31,7 +31,8 @@ class PointCloudGenerator(_Processor):
     def __init__(self, config_manager, az_antenna_idxs: Union[List[int], np.ndarray],
                  el_antenna_idxs: Union[List[int], np.ndarray], detector_type: str = "range_doppler_detector_2d",
                  detector_params: Dict = {}, shift_az_resp: bool = True, shift_el_resp: bool = False,
-                 num_angle_bins: int = 64, tdm_compensation: bool = False, tdm_tx_slots=None, **kwargs):
+                 num_angle_bins: int = 64, tdm_compensation: bool = False, tdm_tx_slots=None, tdm_velocity_unwrap: bool = False,
+                 tdm_hypothesis_list="az", **kwargs):
         # TDM-MIMO Doppler phase compensation of the angle estimates (no upstream counterpart); off: the reference
         self.tdm_compensation = bool(tdm_compensation)
         self.tdm_slots = None
@@ -44,6 +45,18 @@ class PointCloudGenerator(_Processor):
         self.shift_el_resp = shift_el_resp
         self.az_antenna_idxs = _as_index_array(az_antenna_idxs, "az_antenna_idxs")
         self.el_antenna_idxs = _as_index_array(el_antenna_idxs, "el_antenna_idxs")
+        # TDM-MIMO velocity unwrapping (no upstream counterpart): the Doppler hypothesis of every detection from the
+        # angle peak of the deciding list, v = vel_bins[c] + m * 2 vel_max; tdm_hypotheses holds the last frame's choices
+        self.tdm_velocity_unwrap = bool(tdm_velocity_unwrap)
+        self.tdm_hyp_list = None
+        self.tdm_hypotheses = np.empty(0, dtype=np.int32)
+        if self.tdm_velocity_unwrap:
+            from ..batch import tdm_hypothesis_list_of
+            if not self.tdm_compensation:
+                raise ValueError("PointCloudGenerator: tdm_velocity_unwrap=True chooses among the factors of tdm_compensation=True; "
+                                 "pass both")
+            self.tdm_hyp_list = tdm_hypothesis_list_of(tdm_hypothesis_list, [int(i) for i in self.az_antenna_idxs],
+                                                       [int(i) for i in self.el_antenna_idxs], self.tdm_slots)
         self.num_angle_bins = num_angle_bins
         self.phase_shifts = None
         self.angle_bins = None
@@ -79,12 +92,20 @@ class PointCloudGenerator(_Processor):
                 return self._convert_to_cartesian(det_ranges, az, el, det_velocities)
         dets = det.process(adc_cube, **kwargs)
         if dets.shape[0] == 0:
+            self.tdm_hypotheses = np.empty(0, dtype=np.int32)
             return np.empty((0, 4))
         det_ranges, det_velocities, r_idx, v_idx = det._map_detections_to_bins(dets)
         # (None = "the cube the detector has just left on the device": passing detector.rng_dop_resp_raw, as the reference
         #  does, would first download and convert it)
         az, el = self._compute_angle_estimation(None if getattr(det, "_dev", None) is not None else det.rng_dop_resp_raw,
                                                 r_idx, v_idx)
+        if self.tdm_velocity_unwrap:        # v + m span where the chosen hypothesis folds; m == 0 keeps the table's bits
+            from ..batch import tdm_unwrapped_bin
+            C = self._tdm_C
+            c = np.asarray(v_idx).astype(np.int64)
+            m = (tdm_unwrapped_bin(c, self.tdm_hypotheses, self.tdm_slots[1], C) - (c - C // 2)) // C
+            det_velocities = np.where(m != 0, det_velocities + m.astype(np.float64) * (2.0 * self.config_manager.vel_max_m_s),
+                                      det_velocities)
         return self._convert_to_cartesian(det_ranges, az, el, det_velocities)
 
     # ------------------------------------------------------------------ angles
@@ -102,7 +123,7 @@ class PointCloudGenerator(_Processor):
         n = len(det_range_idxs)
         az_angles = np.zeros(n)
         el_angles = np.zeros(n)
-        if n == 0 or (self.az_antenna_idxs.size == 0 and self.el_antenna_idxs.size == 0):
+        if n == 0 or (self.az_antenna_idxs.size == 0 and self.el_antenna_idxs.size == 0 and not self.tdm_velocity_unwrap):
             return az_angles, el_angles
         ctx, bufs = self._device()
         L, h = ctx.lib, ctx.handle
@@ -122,6 +143,9 @@ class PointCloudGenerator(_Processor):
             d_l1 = bufs.get("plane_l1", V * 4)
             _lib.check(L.mmw_plane_l1(h, d_cube.ptr, d_l1.ptr, 1, V, S, C))
         self.n_refined = 0
+        if self.tdm_velocity_unwrap:
+            return self._angles_with_hypotheses(ctx, bufs, n, A, d_idx, resident, raw, r_idx, v_idx,
+                                                (d_cube, d_l1, d_rd, d_dets, d_cnt, V, S, C) if resident else None)
         out = []
         for ant, shift in ((self.az_antenna_idxs, self.shift_az_resp), (self.el_antenna_idxs, self.shift_el_resp)):
             if ant.size == 0:
@@ -157,6 +181,46 @@ class PointCloudGenerator(_Processor):
                 _lib.check(L.mmw_angle_argmax_cells64(h, d_cells.ptr, d_idx.ptr, n, cells.shape[1], A, int(bool(shift))))
             out.append(self.angle_bins[d_idx.download((n,), np.int32).astype(int)])
         return out[0], out[1]
+
+    def _angles_with_hypotheses(self, ctx, bufs, n, A, d_idx, resident, raw, r_idx, v_idx, dev):
+        """``tdm_velocity_unwrap=True``: the deciding list through every hypothesis (``mmw_angle_argmax_tdm_hyp`` on the resident
+        cube, ``mmw_angle_argmax_cells64_tdm_hyp`` on a caller's cube), then the other lists with the hypothesis given."""
+        from ..batch import tdm_hypothesis_table
+        L, h = ctx.lib, ctx.handle
+        which, deciding = self.tdm_hyp_list
+        slots, n_slots = self.tdm_slots
+        self._tdm_C = C = dev[7] if resident else raw.shape[2]
+        d_hyp = bufs.get("pc_hyp", n * 4)
+        lists = {"az": (self.az_antenna_idxs, self.shift_az_resp), "el": (self.el_antenna_idxs, self.shift_el_resp),
+                 "list": (np.asarray(deciding, dtype=int), False)}
+        if not resident:
+            d_cols = bufs.get("pc_cols", n * 4)
+            d_cols.upload(np.ascontiguousarray(v_idx, dtype=np.int32))
+        angles = {"az": np.zeros(n), "el": np.zeros(n)}
+        for key in (which,) + tuple(k for k in ("az", "el") if k != which):
+            ant, shift = lists[key]
+            if ant.size == 0:
+                continue
+            table = tdm_hypothesis_table(ant, slots, n_slots, C)
+            given = int(key != which)
+            if resident:
+                d_cube, d_l1, d_rd, d_dets, d_cnt, V, S, _ = dev
+                arr, n_ant = _lib.int_array(ant)
+                n_ref = _lib.C.c_int(0)
+                _lib.check(L.mmw_angle_argmax_tdm_hyp(h, d_cube.ptr, d_l1.ptr, d_rd.ptr, d_dets.ptr, d_cnt.ptr, d_idx.ptr, d_hyp.ptr, given, 1,
+                                                      V, S, C, n, arr, n_ant, A, int(bool(shift)), table.ctypes.data, n_slots,
+                                                      _lib.C.byref(n_ref)))
+                self.n_refined += n_ref.value
+            else:
+                cells = np.ascontiguousarray(raw[ant][:, r_idx, v_idx].T, dtype=np.complex128)
+                d_cells = bufs.get("pc_cells", cells.nbytes)
+                d_cells.upload(cells)
+                _lib.check(L.mmw_angle_argmax_cells64_tdm_hyp(h, d_cells.ptr, d_cols.ptr, table.ctypes.data, n_slots, d_idx.ptr, d_hyp.ptr,
+                                                              given, n, cells.shape[1], C, A, int(bool(shift))))
+            if key in angles:
+                angles[key] = self.angle_bins[d_idx.download((n,), np.int32).astype(int)]
+        self.tdm_hypotheses = d_hyp.download((n,), np.int32).copy()
+        return angles["az"], angles["el"]
 
     def _convert_to_cartesian(self, ranges, az_angles, el_angles, velocities) -> np.ndarray:
         """FLU frame: x forward, y left, z up (reference :216-248).  O(N) host arithmetic on the detections."""
